@@ -9,7 +9,7 @@ REC_MLM_CPT forward over one batch already resident in HBM, producing the [MASK]
 
     python bench.py [--gpus N --steps K --warmup W] [--batch 64] [--dtype bf16|fp32] [--all-rows]
 N > 1: one rank per GPU under torch.distributed.run (RCCL) -- the driver launches it that way, and a
-bare `python bench.py --gpus N` re-executes itself the same way.  Inference shards sequences across
+bare `python bench.py --gpus N` relaunches itself the same way (as a child process).  Inference shards sequences across
 ranks with no data-path collective (weak scaling: 64 sequences per GPU); --mode train runs the
 few-shot step data-parallel (bucketed reduce-scatter under backward, sharded AdamW, all-gather).
 """
@@ -143,6 +143,38 @@ def live_pmc_traffic(kernel, timeout_s=240):
         return None, "live PMC passes failed: %r" % (e,)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
+
+
+DUMP_BYTES = 64 << 20           # --dump-outputs: at most this much in all (every rank together)
+
+
+def dump_outputs(path, arrays, rank=0, world=1, seed=88):
+    """--dump-outputs: `arrays` ({name: tensor}, what the timed path handed its caller in the last timed step) as path/<name>.npy
+    (path/<name>_rank<r>.npy with more than one rank), float64 kept, everything else float32.  An array larger than its share of
+    DUMP_BYTES is stored as a fixed seeded sample of its flattened elements (sorted flat indices; same shape -> same indices on
+    every run and every build).  Returns {name: {"shape": [...], "stored": n_elements, "sampled": bool}}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BYTES // max(world, 1)
+    info = {}
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel())          # small arrays first: whatever they leave goes to the large ones
+    for i, (name, t) in enumerate(todo):
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        esz = 8 if dt == torch.float64 else 4
+        n = t.numel()
+        k = min(n, left // esz // (len(todo) - i))
+        flat = t.reshape(-1)
+        if k < n:
+            rng = np.random.Generator(np.random.PCG64([seed, n]))
+            idx = np.unique(rng.integers(0, n, size=k, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = (flat if k < n else t).to(dt).cpu().numpy()
+        left -= a.nbytes
+        fn = name if world == 1 else "%s_rank%d" % (name, rank)
+        np.save(os.path.join(path, fn + ".npy"), a)
+        info[fn] = {"shape": list(t.shape), "stored": int(a.size), "sampled": bool(k < n)}
+    return info
 
 
 def gemm_flops(kind, M, H, I):
@@ -562,7 +594,13 @@ def main():
     ap.add_argument("--force-collectives", action="store_true",
                     help="debug, train mode at one rank: run the reduce-scatter / all-gather of the data-parallel step anyway (RCCL with one rank) so that the "
                          "`comm` block of the line can be exercised on a 1-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all; larger arrays as a fixed seeded sample) -- the same arguments give the same inputs on every run "
+                         "(training outputs then agree to rounding only: the backward adds some gradients with atomics)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: one rank per GPU under torch.distributed.run (the same command line the driver uses)
@@ -577,8 +615,9 @@ def main():
         if args.print_launch:
             print(" ".join(cmd))
             return
+        import subprocess
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-        os.execvpe(sys.executable, cmd, env)
+        sys.exit(subprocess.call(cmd, env=env))      # a fresh child process, never exec over this one
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -616,6 +655,7 @@ def main():
         k, v = kv.split("=")
         _lib.check(_lib.lib().cpt_set_tuning(int(k), int(v)), "cpt_set_tuning")
     seed = 88
+    torch.manual_seed(seed)         # module init and the training dropout key (train.dropout_for): the same inputs on every run
     train = args.mode == "train"
     Lt, Li = 70, 50
     if args.workload == "vcr":
@@ -658,24 +698,25 @@ def main():
     nsp_labels = (torch.arange(B, device=dev) % 3).to(torch.int64)       # VCR: relation label per (question, choice) sequence
 
     def step():
+        """One step; returns {name: tensor}, what the caller of the path receives (the last entry: the logits / relation scores)."""
         if train and args.workload == "vcr":     # fewshot/vcr_nsp_cpt.py:425-470: relation-label cross entropy through the NSP-CPT head
             opt.zero_grad()
             loss, logits = model(b["input_ids"], b["segment_ids"], b["attention_mask"], nsp_labels, img_feats=b["img_feats"])
             loss.backward()
             opt.step()
-            return logits
+            return {"loss": loss, "relation_scores": logits}
         if train:
             opt.zero_grad()
             loss, logits = model(b["input_ids"], b["segment_ids"], b["attention_mask"], img_feats=b["img_feats"],
                                  masked_lm_labels=b["colors"], mask_token_pos=b["mask_token_pos"])
             loss.backward()
             opt.step()                      # world > 1: sharded AdamW + parameter all-gather (reduce-scatter ran under backward)
-            return logits
+            return {"loss": loss, "logits": logits}
         with torch.no_grad():
             if args.workload == "vcr":
-                return model(b["input_ids"], b["segment_ids"], b["attention_mask"], img_feats=b["img_feats"])[0]
-            return model(b["input_ids"], b["segment_ids"], b["attention_mask"], img_feats=b["img_feats"],
-                         mask_token_pos=mpos)[0]
+                return {"relation_scores": model(b["input_ids"], b["segment_ids"], b["attention_mask"], img_feats=b["img_feats"])[0]}
+            return {"logits": model(b["input_ids"], b["segment_ids"], b["attention_mask"], img_feats=b["img_feats"],
+                                    mask_token_pos=mpos)[0]}
 
     def barrier():
         if world > 1:
@@ -683,13 +724,22 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        out = step()
+        res = step()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        out = step()
+        res = step()
     barrier()
     dt = time.perf_counter() - t0
+    out = list(res.values())[-1]
+    dumped = None
+    if args.dump_outputs:
+        # before anything else runs on the model: the steps below (sustained, profiles, side configurations) overwrite these buffers,
+        # and in training they move the weights.  Training also hands the caller the parameters AdamW updated in place.
+        if train:
+            res = dict(res, parameters=torch.cat([p.detach().reshape(-1) for p in model.parameters()]))
+        dumped = dump_outputs(args.dump_outputs, res, rank, world, seed)
+        del res
     assert args.no_check or torch.isfinite(out).all()
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -806,6 +856,8 @@ def main():
                 "roofline": roof, "kernel_ms_per_step": breakdown, "kernel_ms_note": breakdown_note if breakdown else None}
         if comm is not None:
             line["comm"] = comm
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if args.workload != "refcoco":
             line["metric"] = "prompted (image,query) pairs/sec, %s workload (not the headline configuration)" % args.workload
         if n_gpus == 1 and not args.no_roofline and not train and args.workload == "refcoco":

@@ -151,7 +151,12 @@ def test_large_vcr_shape(golden_dir):
     ren = {"cls.seq_relationship.weight": "cls.weight", "cls.seq_relationship.bias": "cls.bias"}       # NSPCPT's cls IS the relation Linear
     grads = {ren.get(k, k): v.grad for k, v in sd.items()}
     assert _check_grad_norms(g, grads) > 370
-    np.testing.assert_allclose(grads["cls.weight"].numpy(), g["grad_cls_weight"], atol=1e-7, rtol=2e-3)
+    # The fixture is itself an fp32 result: it lies up to 8.5e-7 (relative Frobenius 1.2e-6) from the same gradient in float64, so the
+    # absolute floor sits above that, where the host's BLAS kernels and thread count no longer decide the outcome; the norm bound
+    # below catches any error spread over the whole matrix.
+    gw = grads["cls.weight"].double().numpy()
+    np.testing.assert_allclose(gw, g["grad_cls_weight"], atol=2e-6, rtol=2e-3)
+    assert np.linalg.norm(gw - g["grad_cls_weight"]) < 1e-5 * np.linalg.norm(g["grad_cls_weight"])
     np.testing.assert_allclose(grads["bert.pooler.dense.weight"][:8, :16].numpy(), g["grad_sample_pooler"], atol=1e-8, rtol=2e-3)
     np.testing.assert_allclose(grads["bert.encoder.layer.23.attention.self.query.weight"][:8, :16].numpy(), g["grad_sample_q23"], atol=1e-8, rtol=2e-3)
     np.testing.assert_allclose(grads["bert.encoder.layer.0.intermediate.dense.weight"][:8, :16].numpy(), g["grad_sample_ffn0"], atol=1e-8, rtol=2e-3)
