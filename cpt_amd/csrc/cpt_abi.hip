@@ -464,8 +464,9 @@ int enc_rows(const cpt_dims& d, int B, int Lt, int Li, int flags) {
 }
 }  // namespace
 
-int cpt_model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* o, int flags,
-                  void* workspace, size_t workspace_bytes, void* stream) {
+// seq_in_ws (cpt_model_fwd_rows): with CPT_OUT_SEQ the encoder output stays in the workspace (x_f32 / x_lp of fwd_layout), o->seq is not used
+static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* o, int flags,
+                     void* workspace, size_t workspace_bytes, void* stream, bool seq_in_ws) {
     if (!m || !b || !o || !workspace) return fail(CPT_ERR_NULL, "cpt_model_fwd: null argument");
     const cpt_dims& d = m->dims;
     hipStream_t s = (hipStream_t)stream;
@@ -762,7 +763,7 @@ int cpt_model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* o, 
           TRY(cpt::layernorm_rows(pre, y.ln2_g, y.ln2_b, d.ln_eps, (lpr && !(last && (flags & CPT_OUT_SEQ))) ? nullptr : x_f32, lp ? x_lp : nullptr, dt, M, H, M, 0, 0, s), "layernorm(ffn)"); }
     }
 
-    if (flags & CPT_OUT_SEQ) {
+    if ((flags & CPT_OUT_SEQ) && !seq_in_ws) {
         if (!o->seq) return fail(CPT_ERR_NULL, "cpt_model_fwd: seq output is NULL");
         hipError_t e = hipMemcpyAsync(o->seq, x_f32, (size_t)M * H * 4, hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) return fail(CPT_ERR_HIP - (int)e, "copy sequence_output: %s", hipGetErrorString(e));
@@ -851,6 +852,123 @@ int cpt_model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* o, 
         }
     }
     return CPT_OK;
+}
+
+int cpt_model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* o, int flags,
+                  void* workspace, size_t workspace_bytes, void* stream) {
+    return model_fwd(m, b, o, flags, workspace, workspace_bytes, stream, false);
+}
+
+// ---- MLM head on a list of rows + full-vocabulary log-sum-exp (VG-CPT predicate scoring) -----------------------------------------
+// The encoder runs as cpt_model_fwd with CPT_OUT_SEQ (the whole last layer; its output stays in the workspace), the head rows are gathered
+// by (sequence, position), then transform + LayerNorm as the all-row head, then the mode's decoder GEMM over all V columns -- into `logits`
+// itself without a column list, else into the workspace -- and one pass per row for the log-sum-exp (head_lse.hip row_lse).
+namespace {
+struct RowsLayout { size_t enc, g, t1, t2, split, full, total; };
+RowsLayout rows_layout(const cpt_dims& d, int B, int Lt, int Li, int R, int n_cols, int enc_flags) {
+    const size_t H = d.hidden, V = d.vocab;
+    RowsLayout w;
+    size_t o = al(fwd_layout(d, B, Lt, Li, enc_flags).total);
+    auto take = [&](size_t bytes) { size_t p = o; o += al(bytes); return p; };
+    w.enc = 0;
+    w.g = take((size_t)R * H * 4);
+    w.t1 = take((size_t)R * H * 4);
+    w.t2 = take((size_t)R * H * 4);
+    w.split = d.dtype == CPT_BF16X3 ? take((size_t)R * 3 * H * 2) : 0;
+    w.full = n_cols > 0 ? take((size_t)R * V * 4) : 0;
+    w.total = o;
+    return w;
+}
+}  // namespace
+
+size_t cpt_fwd_rows_workspace_bytes(const cpt_dims* d, int B, int Lt, int Li, int n_rows, int n_cols) {
+    if (!d || B <= 0 || Lt <= 0 || Li < 0 || n_rows <= 0 || n_cols < 0) return 0;
+    // (a [B][L][L] mask never pads the encoder's rows: the 2-D layout is the larger one)
+    return std::max(rows_layout(*d, B, Lt, Li, n_rows, n_cols, CPT_OUT_SEQ).total,
+                    rows_layout(*d, B, Lt, Li, n_rows, n_cols, CPT_OUT_SEQ | CPT_ATTN_MASK_3D).total);
+}
+
+int cpt_model_fwd_rows(const cpt_model* m, const cpt_batch* b, const int64_t* cols, int n_cols, float* logits, float* row_lse,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    if (!m || !b) return fail(CPT_ERR_NULL, "cpt_model_fwd_rows: null argument");
+    const cpt_dims& d = m->dims;
+    hipStream_t s = (hipStream_t)stream;
+    const int B = b->B, Lt = b->Lt, Li = b->Li, L = Lt + Li, R = b->n_rows, H = d.hidden, V = d.vocab;
+    if (B <= 0 || Lt <= 0 || Li < 0) return fail(CPT_ERR_SHAPE, "cpt_model_fwd_rows: bad batch shape B=%d Lt=%d Li=%d", B, Lt, Li);
+    if (d.dtype != CPT_F32 && d.dtype != CPT_BF16 && d.dtype != CPT_BF16X3) return fail(CPT_ERR_DTYPE, "cpt_model_fwd_rows: dtype %d", d.dtype);
+    if (R <= 0) return fail(CPT_ERR_SHAPE, "cpt_model_fwd_rows: n_rows %d must be > 0", R);
+    if (!logits) return fail(CPT_ERR_NULL, "cpt_model_fwd_rows: logits is NULL");
+    if ((long)R > (long)B * L) return fail(CPT_ERR_SHAPE, "cpt_model_fwd_rows: n_rows %d > B * L = %ld", R, (long)B * L);
+    if (!b->row_seq || !b->mask_pos) return fail(CPT_ERR_NULL, "cpt_model_fwd_rows: row_seq and mask_pos are required");
+    if (cols && (n_cols <= 0 || n_cols > V)) return fail(CPT_ERR_SHAPE, "cpt_model_fwd_rows: n_cols %d outside (0, %d]", n_cols, V);
+    if (!m->w_tr || !m->w_dec) return fail(CPT_ERR_NULL, "cpt_model_fwd_rows: model has no MLM head");
+    if (!workspace) return fail(CPT_ERR_NULL, "cpt_model_fwd_rows: null workspace");
+    const int nc = cols ? n_cols : 0;
+    const int eflags = CPT_OUT_SEQ | (b->mask_3d ? CPT_ATTN_MASK_3D : 0);
+    const RowsLayout w = rows_layout(d, B, Lt, Li, R, nc, eflags);
+    if (workspace_bytes < w.total) return fail(CPT_ERR_WORKSPACE, "cpt_model_fwd_rows: workspace %zu < required %zu bytes", workspace_bytes, w.total);
+    if ((uintptr_t)workspace & 255) return fail(CPT_ERR_ALIGN, "cpt_model_fwd_rows: workspace must be 256-byte aligned");
+    {   // the row list and the column list, checked on the host
+        std::vector<int64_t> rs((size_t)R), mp((size_t)R), cl((size_t)(cols ? n_cols : 0));
+        hipError_t e = hipMemcpyAsync(rs.data(), b->row_seq, (size_t)R * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(mp.data(), b->mask_pos, (size_t)R * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && cols) e = hipMemcpyAsync(cl.data(), cols, (size_t)n_cols * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return fail(CPT_ERR_HIP - (int)e, "cpt_model_fwd_rows: read row list: %s", hipGetErrorString(e));
+        for (int r = 0; r < R; ++r) {
+            if (rs[r] < 0 || rs[r] >= B || (r > 0 && rs[r] < rs[r - 1]))
+                return fail(CPT_ERR_SHAPE, "cpt_model_fwd_rows: row_seq[%d] = %lld: must be ascending in [0, %d)", r, (long long)rs[r], B);
+            if (mp[r] < 0 || mp[r] >= L)
+                return fail(CPT_ERR_SHAPE, "cpt_model_fwd_rows: mask_pos[%d] = %lld outside [0, %d)", r, (long long)mp[r], L);
+        }
+        for (size_t j = 0; j < cl.size(); ++j)
+            if (cl[j] < 0 || cl[j] >= V)
+                return fail(CPT_ERR_SHAPE, "cpt_model_fwd_rows: cols[%zu] = %lld outside [0, %d)", j, (long long)cl[j], V);
+    }
+    unsigned char* ws = (unsigned char*)workspace;
+    cpt_outputs o;
+    memset(&o, 0, sizeof(o));
+    int rc = model_fwd(m, b, &o, eflags, workspace, workspace_bytes, stream, true);
+    if (rc != CPT_OK) return rc;
+
+    Scope p(CPT_K_HEAD, s);
+    const bool x3 = d.dtype == CPT_BF16X3;
+    const int dt = x3 ? CPT_F32 : d.dtype;
+    const bool lp = dt == CPT_BF16;
+    void* splitbuf = ws + w.split;
+    auto gm = [&](int epi, const void* A, const void* W, const float* bias, float* out, int N) -> int {      // [R][H] x [N][H]^T, fp32 out
+        if (!x3) return cpt::gemm(dt, epi, A, H, W, H, bias, nullptr, 0, out, CPT_F32, N, R, N, H, s);
+        const int rc2 = cpt::split3((const float*)A, H, splitbuf, R, H, 0, s);
+        if (rc2 != CPT_OK) return rc2;
+        return cpt::gemm(CPT_BF16, epi, splitbuf, 3 * H, W, 3 * H, bias, nullptr, 0, out, CPT_F32, N, R, N, 3 * H, s);
+    };
+    const FwdLayout fl = fwd_layout(d, B, Lt, Li, eflags);
+    void* g = ws + w.g;
+    float* t1 = (float*)(ws + w.t1);
+    void* t2 = ws + w.t2;
+    // x_lp: the encoder output (LayerNorm'ed) in the compute dtype, row-major [B * L][H] (fp32 and bf16x3: the x_f32 region itself)
+    TRY(cpt::gather_rows(ws + fl.x_lp, dt, b->mask_pos, g, R, L, H, s, b->row_seq, B), "gather(head rows)");
+    TRY(gm(CPT_EPI_GELU, g, m->w_tr, m->b_tr, t1, H), "gemm(head transform)");
+    TRY(cpt::layernorm_rows(t1, m->tr_ln_g, m->tr_ln_b, d.ln_eps, lp ? nullptr : (float*)t2, lp ? t2 : nullptr, dt, R, H, R, 0, 0, s), "layernorm(head)");
+    if (!cols) {
+        TRY(gm(CPT_EPI_NONE, t2, m->w_dec, m->b_dec, logits, V), "gemm(decoder)");
+        if (row_lse) TRY(cpt::row_lse(logits, row_lse, R, V, s), "row log-sum-exp");
+    } else {
+        float* full = (float*)(ws + w.full);
+        TRY(gm(CPT_EPI_NONE, t2, m->w_dec, m->b_dec, full, V), "gemm(decoder)");
+        if (row_lse) TRY(cpt::row_lse(full, row_lse, R, V, s), "row log-sum-exp");
+        TRY(cpt::gather_cols(full, cols, logits, R, n_cols, V, s), "gather(column list)");
+    }
+    return CPT_OK;
+}
+
+int cpt_mean_logprob_scores(const float* logits, int n_cols, int n_rows, const float* row_lse, const int32_t* slot_row, int G, int K,
+                            const int32_t* cand_cols, const int32_t* cand_len, int C, float* out, void* stream) {
+    if (!logits || !row_lse || !slot_row || !cand_cols || !cand_len || !out) return fail(CPT_ERR_NULL, "cpt_mean_logprob_scores: null argument");
+    if (n_cols <= 0 || n_rows <= 0 || G <= 0 || K <= 0 || C <= 0)
+        return fail(CPT_ERR_SHAPE, "cpt_mean_logprob_scores: n_cols %d n_rows %d G %d K %d C %d", n_cols, n_rows, G, K, C);
+    return check_launch(cpt::mean_logprob(logits, n_cols, n_rows, row_lse, slot_row, G, K, cand_cols, cand_len, C, out, (hipStream_t)stream),
+                        "cpt_mean_logprob_scores");
 }
 
 }  // extern "C"

@@ -290,4 +290,10 @@ struct OverrideScope {
 void set_gemm_trace(void* p);
 void set_gemm_trace_filter(int epi, int k);
 
+// head_lse.hip: MLM head rows with the full-vocabulary normaliser (cpt_model_fwd_rows, cpt_mean_logprob_scores)
+int row_lse(const float* x, float* lse, int R, int V, hipStream_t s);                                       // from full fp32 rows [R][V]
+int gather_cols(const float* x, const int64_t* cols, float* out, int R, int n, int V, hipStream_t s);      // out[r][j] = x[r][cols[j]]
+int mean_logprob(const float* logits, int n_cols, int n_rows, const float* lse, const int32_t* slot_row, int G, int K, const int32_t* cand_cols,
+                 const int32_t* cand_len, int C, float* out, hipStream_t s);
+
 }  // namespace cpt

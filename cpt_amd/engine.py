@@ -520,6 +520,67 @@ class PackedModel(object):
             out["loss"] = acc[0] / acc[1]       # mean over labelled rows (CrossEntropyLoss default)
         return out
 
+    def forward_rows(self, input_ids, token_type_ids=None, attention_mask=None, position_ids=None, img_feats=None,
+                     row_seq=None, mask_pos=None, cols=None, lse=True):
+        """MLM head on n head rows (include/cpt_hip.h cpt_model_fwd_rows): row r is position mask_pos[r] of sequence row_seq[r]
+        (row_seq ascending, any number of rows per sequence).  Returns {"logits": (n, len(cols)) -- or (n, V) without cols --,
+        "lse": (n,) natural-log log-sum-exp of each row over all V columns (None with lse=False)}."""
+        self.ensure_packed()
+        self.refresh_shadow()
+        if self.dtype == "bf16" and self.fold_ln:
+            self.ensure_fold()
+        dev = self.flat.device
+
+        def prep(t, dt, name):
+            if t is None:
+                return None
+            if not t.is_cuda:
+                raise RuntimeError("cpt_amd: %s is on %s; inputs must be on the GPU" % (name, t.device))
+            return t.to(dt).contiguous()
+
+        if row_seq is None or mask_pos is None:
+            raise RuntimeError("cpt_amd: forward_rows needs row_seq and mask_pos")
+        input_ids = prep(input_ids, torch.int64, "input_ids")
+        token_type_ids = prep(token_type_ids, torch.int64, "token_type_ids")
+        position_ids = prep(position_ids, torch.int64, "position_ids")
+        mask3 = attention_mask is not None and attention_mask.dim() == 3
+        if attention_mask is not None and attention_mask.dim() not in (2, 3):
+            raise NotImplementedError("cpt_amd: attention_mask must be 2-D or 3-D (modeling_bert.py:213-218)")
+        attention_mask = prep(attention_mask, torch.int64, "attention_mask")
+        img_feats = prep(img_feats, torch.float32, "img_feats")
+        row_seq = prep(row_seq.reshape(-1), torch.int64, "row_seq")
+        mask_pos = prep(mask_pos.reshape(-1), torch.int64, "mask_pos")
+        if row_seq.numel() != mask_pos.numel():
+            raise RuntimeError("cpt_amd: row_seq has %d entries, mask_pos %d" % (row_seq.numel(), mask_pos.numel()))
+        B, Lt = input_ids.shape
+        Li = img_feats.size(1) if img_feats is not None else 0
+        Lseq = Lt + Li
+        if img_feats is not None and img_feats.size(2) != self.cfg.img_feature_dim:
+            raise RuntimeError("cpt_amd: img_feats last dim %d != config.img_feature_dim %d"
+                               % (img_feats.size(2), self.cfg.img_feature_dim))
+        want = (B, Lseq, Lseq) if mask3 else (B, Lseq)
+        if attention_mask is not None and tuple(attention_mask.shape) != want:
+            raise RuntimeError("cpt_amd: attention_mask shape %s != %s" % (tuple(attention_mask.shape), want))
+        V = self.cfg.vocab_size
+        n = row_seq.numel()
+        if cols is not None:
+            cols = prep(cols.reshape(-1), torch.int64, "cols")
+        nc = cols.numel() if cols is not None else 0
+        m, _ = self.descriptor()
+        out = {"logits": torch.empty((n, nc if cols is not None else V), device=dev, dtype=torch.float32),
+               "lse": torch.empty(n, device=dev, dtype=torch.float32) if lse else None}
+        bt = L.Batch(B=B, Lt=Lt, Li=Li, input_ids=input_ids.data_ptr(), token_type=L.ptr(token_type_ids),
+                     position_ids=L.ptr(position_ids), attn_mask=L.ptr(attention_mask), img_feats=L.ptr(img_feats),
+                     mask_pos=mask_pos.data_ptr(), labels=None, n_rows=n, mask_3d=1 if mask3 else 0, row_seq=row_seq.data_ptr())
+        need = L.lib().cpt_fwd_rows_workspace_bytes(C.byref(m.dims), B, Lt, Li, n, nc) if n > 0 else 0
+        ws = self._ws.get("rows")
+        if need and (ws is None or ws.numel() < need or ws.device != dev):
+            ws = torch.empty(need, device=dev, dtype=torch.uint8)
+            self._ws["rows"] = ws
+        L.check(L.lib().cpt_model_fwd_rows(C.byref(m), C.byref(bt), L.ptr(cols), nc, out["logits"].data_ptr(), L.ptr(out["lse"]),
+                                           L.ptr(ws), ws.numel() if ws is not None else 0, L.stream_ptr()), "cpt_model_fwd_rows")
+        return out
+
 
 def profile_read():
     """{kernel name: (total_ms, launches)} accumulated since cpt_prof_enable(1)."""

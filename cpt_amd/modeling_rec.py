@@ -9,6 +9,12 @@ head (B x L x 30522 fp32 = 938 MB at B=64) and every caller then keeps only the 
 (zeroshot/refcoco_cpt.py:219, fewshot/refcoco_cpt.py:268, gqa_cpt.py:598-600).  Passing
 ``mask_token_pos`` (B,) returns exactly those rows, (B, V); without it the full
 (B, L, V) tensor is produced as in the reference.
+
+Several head rows per sequence (VG-CPT, fewshot/vg_cpt.py:136-160, 271-290): ``mask_token_pos`` as an (n, 2) long tensor of
+(sequence, position) pairs -- the format of vg_cpt.train_collate -- returns the n rows, (n, V) or (n, len(vocab_columns)).
+``log_softmax=True`` (with either form of ``mask_token_pos``) returns log-probabilities over the full vocabulary at those
+columns: the normaliser is computed on the device over all V columns (include/cpt_hip.h cpt_model_fwd_rows) without the
+(n, V) scores being returned.
 """
 import torch
 from torch import nn
@@ -42,10 +48,13 @@ class REC_MLM_CPT(_EngineMixin, BertPreTrainedModel):
         self._tie_or_clone_weights(self.cls.decoder, self.bert.embeddings.word_embeddings)
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, masked_lm_labels=None,
-                position_ids=None, head_mask=None, img_feats=None, mask_token_pos=None, vocab_columns=None):
+                position_ids=None, head_mask=None, img_feats=None, mask_token_pos=None, vocab_columns=None, log_softmax=False):
         # vocab_columns (extension, inference with mask_token_pos only): 1-D tensor of vocabulary ids -- the returned scores are (B, len(vocab_columns)),
         # those columns of the (B, V) prediction scores in list order (the drivers read colour-token columns only: zeroshot/refcoco_cpt.py:219)
         _check_unsupported(self.config, head_mask, None)
+        if log_softmax or (mask_token_pos is not None and mask_token_pos.dim() == 2):
+            return self._forward_rows(input_ids, token_type_ids, attention_mask, masked_lm_labels, position_ids, img_feats,
+                                      mask_token_pos, vocab_columns, log_softmax)
         rows = mask_token_pos is not None
         flags = L.OUT_MASK_LOGITS if rows else L.OUT_ALL_LOGITS
         labels = None
@@ -81,3 +90,32 @@ class REC_MLM_CPT(_EngineMixin, BertPreTrainedModel):
         if masked_lm_labels is not None:
             outputs = (out["loss"],) + outputs
         return outputs
+
+    def _forward_rows(self, input_ids, token_type_ids, attention_mask, masked_lm_labels, position_ids, img_feats, mask_token_pos,
+                      vocab_columns, log_softmax):
+        """Inference on (sequence, position) head rows; see the module docstring."""
+        if masked_lm_labels is not None:
+            raise NotImplementedError("cpt_amd: (n, 2) mask_token_pos / log_softmax are inference forms (train through the (B, L) label grid)")
+        if mask_token_pos is None:
+            raise NotImplementedError("cpt_amd: log_softmax needs mask_token_pos (the head rows)")
+        if mask_token_pos.dim() == 2:
+            if mask_token_pos.size(1) != 2:
+                raise ValueError("cpt_amd: mask_token_pos must be (B,) or (n, 2) (sequence, position) pairs")
+            seq, pos = mask_token_pos[:, 0], mask_token_pos[:, 1]
+        else:
+            pos = mask_token_pos
+            seq = torch.arange(pos.numel(), device=pos.device)
+        order = None
+        if seq.numel() > 1 and not bool((seq[1:] >= seq[:-1]).all()):
+            order = torch.argsort(seq, stable=True)        # the library takes the rows grouped by ascending sequence
+            seq, pos = seq[order], pos[order]
+        out = self._engine().forward_rows(input_ids, token_type_ids, attention_mask, position_ids, img_feats, row_seq=seq,
+                                          mask_pos=pos, cols=vocab_columns, lse=log_softmax)
+        scores = out["logits"]
+        if log_softmax:
+            scores = scores - out["lse"][:, None]
+        if order is not None:
+            back = torch.empty_like(order)
+            back[order] = torch.arange(order.numel(), device=order.device)
+            scores = scores[back]
+        return (scores,)

@@ -102,3 +102,111 @@ def argmax_columns_device(scores, ids):
     L.check(L.lib().cpt_argmax_columns(sc.data_ptr(), V, idt.data_ptr(), idt.numel(), R, out.data_ptr(), None, L.stream_ptr()),
             "cpt_argmax_columns")
     return out
+
+
+# ---- VG-CPT predicate scoring (Oscar/oscar/fewshot/vg_cpt.py:255-290) ----------------------------------------------------------
+# Every (subject, object) pair gives 6 sequences: "S is [MASK] x k a O" for k = 1, 2, 3, then the same with S and O swapped
+# (datasets/vg_test_dataset.py), i.e. 1 + 2 + 3 head rows per direction, 12 per pair, in sequence order.  A predicate of n
+# word-pieces is scored on the n-mask template as the mean log-probability (softmax over all V columns) of its pieces.
+VG_MAX_PIECES = 3
+
+
+def vg_candidates(idx2pred):
+    """idx2pred {predicate index: [word-piece ids]} (vg_cpt.py:260-262) -> (cols, cand_cols (C, 3) int32, cand_len (C,) int32):
+    cols = the sorted union of the word-piece ids (the decoder columns to compute), cand_cols[c][j] = position of piece j of
+    predicate c in cols.  C = max index + 1; indices without a predicate (0: background) have length 0.  Raises on a predicate
+    of more than 3 pieces (the reference would fail with an IndexError: there is no such template)."""
+    for idx, pieces in idx2pred.items():
+        if not 1 <= len(pieces) <= VG_MAX_PIECES:
+            raise ValueError("cpt_amd: predicate %s has %d word-pieces; VG templates hold 1 to %d [MASK]s" % (idx, len(pieces), VG_MAX_PIECES))
+    cols = sorted({int(t) for pieces in idx2pred.values() for t in pieces})
+    where = {t: i for i, t in enumerate(cols)}
+    C = max(int(i) for i in idx2pred) + 1
+    cand_cols = torch.zeros((C, VG_MAX_PIECES), dtype=torch.int32)
+    cand_len = torch.zeros(C, dtype=torch.int32)
+    for idx, pieces in idx2pred.items():
+        cand_len[int(idx)] = len(pieces)
+        for j, t in enumerate(pieces):
+            cand_cols[int(idx), j] = where[int(t)]
+    return torch.tensor(cols, dtype=torch.int64), cand_cols, cand_len
+
+
+def vg_slot_rows(n_pairs):
+    """(2 * n_pairs, 3) int32: first head row of the k-mask template (column k - 1) of group g = 2 * pair + direction,
+    for head rows laid out as 6 sequences per pair with k [MASK] rows each (k = 1, 2, 3; forward, then reversed)."""
+    first = torch.tensor([0, 1, 3], dtype=torch.int32)
+    g = torch.arange(2 * n_pairs, dtype=torch.int32)[:, None]
+    return (g * 6 + first[None, :]).contiguous()
+
+
+def vg_slot_rows_from(row_seq, n_seq):
+    """slot_row (2 * n_seq / 6, 3) of an actual head-row list: row_seq (n,) the sequence of every head row, ascending.  Checks the
+    VG layout -- sequence 6 i + 3 d + k - 1 holds exactly k rows (k = 1, 2, 3) -- and raises ValueError otherwise, so that rows are
+    never scored against another template's slots."""
+    seq = torch.as_tensor(row_seq).reshape(-1).cpu().long()
+    if n_seq % 6:
+        raise ValueError("cpt_amd: VG batches hold 6 sequences per pair (got %d sequences)" % n_seq)
+    if seq.numel() and (bool((seq[1:] < seq[:-1]).any()) or int(seq.min()) < 0 or int(seq.max()) >= n_seq):
+        raise ValueError("cpt_amd: head rows must be grouped by ascending sequence in [0, %d)" % n_seq)
+    counts = torch.bincount(seq, minlength=n_seq)
+    want = torch.arange(n_seq) % 3 + 1
+    if not torch.equal(counts, want):
+        bad = int((counts != want).nonzero()[0])
+        raise ValueError("cpt_amd: sequence %d holds %d head rows; the VG layout gives sequence s exactly s %% 3 + 1" % (bad, int(counts[bad])))
+    first = (torch.cumsum(counts, 0) - counts).to(torch.int32)
+    return first.view(-1, 3).contiguous()
+
+
+def mean_logprob_scores_device(logits, row_lse, slot_row, cand_cols, cand_len):
+    """include/cpt_hip.h cpt_mean_logprob_scores, one launch: out[g][c] = mean over the len = cand_len[c] pieces of
+    logits[s + j][cand_cols[c][j]] - row_lse[s + j], s = slot_row[g][len - 1]; 0 for len 0.  logits (n, n_cols) and row_lse (n,)
+    fp32 on the GPU; the int tables are moved there.  Returns (G, C)."""
+    from . import _lib as L
+    if not logits.is_cuda:
+        raise RuntimeError("cpt_amd: mean_logprob_scores_device needs the scores on the GPU (no CPU fallback)")
+    dev = logits.device
+    lg = logits.contiguous().float()
+    ls = row_lse.contiguous().float()
+    sr = slot_row.to(device=dev, dtype=torch.int32).contiguous()
+    cc = cand_cols.to(device=dev, dtype=torch.int32).contiguous()
+    cl = cand_len.to(device=dev, dtype=torch.int32).contiguous()
+    G, K = sr.shape
+    C = cl.numel()
+    if cc.shape != (C, K):
+        raise RuntimeError("cpt_amd: cand_cols shape %s != (%d, %d)" % (tuple(cc.shape), C, K))
+    out = torch.empty((G, C), device=dev, dtype=torch.float32)
+    L.check(L.lib().cpt_mean_logprob_scores(lg.data_ptr(), lg.size(1), lg.size(0), ls.data_ptr(), sr.data_ptr(), G, K, cc.data_ptr(),
+                                            cl.data_ptr(), C, out.data_ptr(), L.stream_ptr()), "cpt_mean_logprob_scores")
+    return out
+
+
+def vg_val_scores_reference(seq_row_logits, idx2pred):
+    """Torch restatement of val()'s scoring loop (vg_cpt.py:271-290) over FULL score rows: seq_row_logits is a list with one
+    (k, V) tensor per sequence (6 per pair, in dataset order), the logits of its k [MASK] rows.  Returns (pairs, 2, C): per pair
+    the forward and the reversed direction's scores (the values of predictions[im_key] and predictions[reverse_imkey(im_key)])."""
+    C = max(int(i) for i in idx2pred) + 1
+    scores = [x.float().softmax(-1) for x in seq_row_logits]
+    n_pairs = len(scores) // 6
+    out = torch.zeros((n_pairs, 2, C))
+    for i in range(n_pairs):
+        for d in range(2):
+            cur = [None] + scores[i * 6 + 3 * d: i * 6 + 3 * d + 3]
+            for idx, pred in idx2pred.items():
+                prob_list = cur[len(pred)][torch.arange(len(pred)), torch.as_tensor(pred)]
+                out[i, d, int(idx)] = torch.mean(torch.log(prob_list))
+    return out
+
+
+def vg_predicate_scores(model, input_ids, segment_ids, attention_mask, img_feats, mask_token_pos, idx2pred):
+    """Device scoring of a batch of VG pairs (6 sequences each): mask_token_pos (n, 2) (sequence, position) of the 12 head rows per
+    pair in sequence order.  forward_rows on the union of the predicate word-pieces (the full-vocabulary normaliser computed on the
+    device), then cpt_mean_logprob_scores.  Returns (pairs, 2, C) on the GPU."""
+    cols, cand_cols, cand_len = vg_candidates(idx2pred)
+    dev = input_ids.device
+    B = input_ids.size(0)
+    slot_row = vg_slot_rows_from(mask_token_pos[:, 0], B)
+    out = model._engine().forward_rows(input_ids, segment_ids, attention_mask, None, img_feats, row_seq=mask_token_pos[:, 0],
+                                       mask_pos=mask_token_pos[:, 1], cols=cols.to(dev), lse=True)
+    n_pairs = B // 6
+    sc = mean_logprob_scores_device(out["logits"], out["lse"], slot_row, cand_cols, cand_len)
+    return sc.view(n_pairs, 2, -1)

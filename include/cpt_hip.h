@@ -198,6 +198,33 @@ int cpt_model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* o, 
                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * MLM head on a list of rows with the full-vocabulary normaliser (Oscar/oscar/fewshot/vg_cpt.py:271-290: several [MASK]
+ * rows per sequence, a softmax over all V columns of each, a handful of columns read).  Added beside ABI 8, no struct changed.
+ * ---------------------------------------------------------------------------------------- */
+/* Workspace of cpt_model_fwd_rows (bytes); n_cols = 0 sizes the call without a column list. */
+size_t cpt_fwd_rows_workspace_bytes(const cpt_dims* d, int B, int Lt, int Li, int n_rows, int n_cols);
+
+/* Inference (CPT_F32, CPT_BF16, CPT_BF16X3): encoder as cpt_model_fwd, then the MLM head on b->n_rows (> 0) rows -- row r is position
+ * b->mask_pos[r] of sequence b->row_seq[r] (ascending; a sequence may have any number of rows, none included).  b->labels is ignored;
+ * b->mask_3d = 1 means attn_mask is [B][L][L] (as CPT_ATTN_MASK_3D).
+ *   logits  [n_rows][n_cols]: the scores of the DEVICE column list `cols` (vocabulary ids, list order, duplicates allowed);
+ *           cols == NULL: [n_rows][V], every column.
+ *   row_lse [n_rows] or NULL: natural-log log-sum-exp of the row's scores over all V columns (with a column list the [n_rows][V] scores
+ *           live in the workspace, cpt_fwd_rows_workspace_bytes).
+ * CPT_ERR_SHAPE: n_rows <= 0, row_seq not ascending or outside [0, B), mask_pos outside [0, L), n_cols > V, a column id outside [0, V).
+ * The call reads row_seq, mask_pos and cols back to the host to check them (it waits for `stream` once; not for graph capture). */
+int cpt_model_fwd_rows(const cpt_model* m, const cpt_batch* b, const int64_t* cols, int n_cols, float* logits, float* row_lse,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* Mean log-probability of candidate word-piece lists over k-[MASK] templates (vg_cpt.py:283-289):
+ *   out[g][c] = (1 / len) sum_{j < len} (logits[(s + j) * n_cols + cand_cols[c * K + j]] - row_lse[s + j]),
+ *   len = cand_len[c], s = slot_row[g * K + len - 1]: the first head row of group g's len-mask template.
+ * len == 0 gives 0 (the background slot); s < 0, s + len > n_rows or a cand_cols entry outside [0, n_cols) gives NaN (never read).
+ * logits [n_rows][n_cols], row_lse [n_rows], slot_row [G][K], cand_cols [C][K], cand_len [C] (int32), out [G][C]; all device. */
+int cpt_mean_logprob_scores(const float* logits, int n_cols, int n_rows, const float* row_lse, const int32_t* slot_row, int G, int K,
+                            const int32_t* cand_cols, const int32_t* cand_len, int C, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Few-shot training step (Oscar/oscar/fewshot/refcoco_cpt.py:231-249): forward that keeps the
  * activations, backward into caller-owned fp32 gradient tensors laid out like the parameters,
  * fused AdamW.  [MASK]-rows mode only (the loss of modeling_rec.py:147-150 sees only those rows).
