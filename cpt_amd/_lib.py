@@ -82,6 +82,8 @@ _SIGS = {
     "cpt_fwd_rows_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "cpt_model_fwd_rows": (C.c_int, [C.POINTER(Model), C.POINTER(Batch), vp, C.c_int, vp, vp, vp, C.c_size_t, vp]),
     "cpt_mean_logprob_scores": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
+    "cpt_vg_recall_workspace_bytes": (C.c_size_t, [vp, C.c_int]),
+    "cpt_vg_recall_ranks": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]),
     "cpt_train_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int, C.c_int]),
     "cpt_train_workspace_bytes_rows": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int, C.c_int, C.c_int]),
     "cpt_train_fwd": (C.c_int, [C.POINTER(Model), C.POINTER(Batch), C.POINTER(Outputs), vp, C.c_size_t, vp]),

@@ -971,4 +971,24 @@ int cpt_mean_logprob_scores(const float* logits, int n_cols, int n_rows, const f
                         "cpt_mean_logprob_scores");
 }
 
+size_t cpt_vg_recall_workspace_bytes(const int32_t* cand_off, int n_img) {
+    if (!cand_off || n_img <= 0) return 0;
+    long long big = 0;
+    for (int i = 0; i < n_img; ++i) {
+        const long long n = (long long)cand_off[i + 1] - cand_off[i];
+        if (n > cpt::vg_recall_tile()) big += n;
+    }
+    return cpt::vg_recall_ws_bytes(big);
+}
+
+int cpt_vg_recall_ranks(const float* scores, int n_rows, int C, const int32_t* cand_off, const int32_t* cand, int n_cand, const int32_t* gt_off,
+                        const int32_t* gt, int n_gt, int n_img, int32_t* out_rank, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!cand_off || !gt_off || (n_rows > 0 && !scores) || (n_cand > 0 && !cand) || (n_gt > 0 && (!gt || !out_rank)))
+        return fail(CPT_ERR_NULL, "cpt_vg_recall_ranks: null argument");
+    if (n_img <= 0 || C < 2 || n_rows < 0 || n_cand < 0 || n_gt < 0)
+        return fail(CPT_ERR_SHAPE, "cpt_vg_recall_ranks: n_img %d C %d n_rows %d n_cand %d n_gt %d", n_img, C, n_rows, n_cand, n_gt);
+    return check_launch(cpt::vg_recall(scores, n_rows, C, cand_off, cand, n_cand, gt_off, gt, n_gt, n_img, out_rank, workspace, workspace_bytes,
+                                       (hipStream_t)stream), "cpt_vg_recall_ranks");
+}
+
 }  // extern "C"

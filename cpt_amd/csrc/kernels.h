@@ -295,5 +295,10 @@ int row_lse(const float* x, float* lse, int R, int V, hipStream_t s);           
 int gather_cols(const float* x, const int64_t* cols, float* out, int R, int n, int V, hipStream_t s);      // out[r][j] = x[r][cols[j]]
 int mean_logprob(const float* logits, int n_cols, int n_rows, const float* lse, const int32_t* slot_row, int G, int K, const int32_t* cand_cols,
                  const int32_t* cand_len, int C, float* out, hipStream_t s);
+// vg_recall.hip: VG Recall@K ranks, one workgroup per image (cpt_vg_recall_ranks)
+int vg_recall(const float* scores, int n_rows, int C, const int32_t* cand_off, const int32_t* cand, int n_cand, const int32_t* gt_off,
+              const int32_t* gt, int n_gt, int n_img, int32_t* out_rank, void* ws, size_t ws_bytes, hipStream_t s);
+size_t vg_recall_ws_bytes(long long n_big);
+int vg_recall_tile();
 
 }  // namespace cpt

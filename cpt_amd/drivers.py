@@ -107,3 +107,86 @@ def train_batch(model, optimizer, batches, opts, device, global_step=0):
         global_step += 1
         losses.append(loss.detach())
     return global_step, losses
+
+
+# ---- VG-CPT (Oscar/oscar/fewshot/vg_cpt.py; launched by cmds/vg/_fsl.sh with 16 pairs per GPU) ------------------------------------
+def _vg_cat(chunk, device, per_pair):
+    """Concatenate pairs (dicts of prompts.assemble_vg_* arrays + img_feats) into one batch; mask_token_pos gets the pair's sequence
+    offset.  img_feats (Li, D) is repeated per sequence on the device (the reference stacks it per sequence)."""
+    t = lambda x: torch.as_tensor(x)
+    out = {k: torch.cat([t(q[k]) for q in chunk], 0).to(device, non_blocking=True) for k in ("input_ids", "segment_ids", "attention_mask")}
+    feats = []
+    for q in chunk:
+        f = t(q["img_feats"]).to(device, non_blocking=True)
+        feats.append(f.unsqueeze(0).expand(per_pair, -1, -1) if f.dim() == 2 else f)
+    out["img_feats"] = torch.cat(feats, 0).contiguous()
+    pos = [t(q["mask_token_pos"]).long() + torch.tensor([per_pair * i, 0]) for i, q in enumerate(chunk)]
+    out["mask_token_pos"] = torch.cat(pos, 0).to(device)
+    return out
+
+
+def val_vg(model, pairs, idx2pred, device, batch_pairs=16):
+    """Zero-shot / evaluation pass of vg_cpt.py:255-305.  pairs: one dict per TSV row -- ``img_key`` (the image name), ``input_ids``
+    (6, Lt), ``segment_ids``, ``attention_mask`` (6, Lt + Li), ``mask_token_pos`` (12, 2) as prompts.assemble_vg_zsl gives them, and
+    ``img_feats`` (Li, D) or (6, Li, D).  Pairs are sharded across ranks as val_queries shards queries; each batch is scored on the
+    device (scoring.vg_predicate_scores) and the fixed-shape (pairs, 2, C) scores are gathered with one all_gather.
+    Returns (scores (pairs, 2, C) fp32 on the device, keys): keys[2 i] = pair i's key, keys[2 i + 1] = its reverse_imkey -- the rows of
+    scores.view(-1, C), in dataset order, as scoring.vg_eval_table takes them."""
+    model.eval()
+    rank, world = cdist.rank_world()
+    lo, hi = cdist.shard_range(len(pairs), rank, world)
+    C = max(int(i) for i in idx2pred) + 1
+    local = torch.zeros((hi - lo, 2, C), dtype=torch.float32, device=device)
+    for start in range(lo, hi, batch_pairs):
+        chunk = pairs[start:min(start + batch_pairs, hi)]
+        b = _vg_cat(chunk, device, 6)
+        with torch.no_grad():
+            sc = scoring.vg_predicate_scores(model, b["input_ids"], b["segment_ids"], b["attention_mask"], b["img_feats"],
+                                             b["mask_token_pos"], idx2pred)
+        local[start - lo:start - lo + len(chunk)] = sc
+    scores = cdist.gather_fixed(local, len(pairs), fill=0)
+    keys = []
+    for q in pairs:
+        keys += [q["img_key"], scoring.reverse_imkey(q["img_key"])]
+    return scores, keys
+
+
+def vg_label_grid(batch):
+    """vg_cpt.py:227-229: a (B, L) grid of -1 with row_labels at the (sequence, position) rows of mask_token_pos (n, 2)."""
+    grid = batch["attention_mask"].new_full(batch["attention_mask"].shape, -1, dtype=torch.long)
+    pos = batch["mask_token_pos"].long()
+    grid[pos[:, 0], pos[:, 1]] = batch["row_labels"].long().view(-1)
+    return grid
+
+
+def vg_schedule(opts, num_train_epochs):
+    """vg_cpt.py:532-533, quirk kept: num_train_steps = num_train_epochs and warmup_steps = int(num_train_epochs / 10), so the rate
+    reaches its 1e-8 floor after num_train_epochs STEPS whatever the data set size.  Sets them on opts and returns it."""
+    opts.num_train_steps = num_train_epochs
+    opts.warmup_steps = int(num_train_epochs / 10)
+    return opts
+
+
+def train_vg_batch(model, optimizer, batches, opts, device, global_step=0):
+    """One pass of vg_cpt.py:217-252 (train_batch) over ``batches``: dicts with img_feats, input_ids, attention_mask, segment_ids,
+    mask_token_pos (n, 2) (sequence, position) and row_labels (n,) -- prompts.assemble_vg_train rows concatenated, 6 labelled rows per
+    pair.  The label grid holds several labelled positions per sequence (the multi-row training path of REC_MLM_CPT.forward); LR
+    schedule (opts from vg_schedule), zero_grad / forward / backward / step and the skipped-step rule as train_batch.
+    Returns (global_step, [loss tensors])."""
+    model.train()
+    losses = []
+    for index, host_batch in enumerate(batches):
+        batch = {name: torch.as_tensor(t).to(device) for name, t in host_batch.items()}
+        _apply_lr(optimizer, get_lr_sched(global_step, opts), getattr(opts, "lr_mul", 1.0))
+        try:
+            optimizer.zero_grad()
+            loss = model(batch["input_ids"], batch["segment_ids"], batch["attention_mask"], img_feats=batch["img_feats"],
+                         masked_lm_labels=vg_label_grid(batch))[0]
+            loss.backward()
+            optimizer.step()
+        except RuntimeError as err:
+            logger.info("step %d of this pass skipped: %s", index, err)
+            continue
+        global_step += 1
+        losses.append(loss.detach())
+    return global_step, losses

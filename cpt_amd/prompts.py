@@ -295,3 +295,102 @@ def assemble_vcr(tokenizer, question, choices, colors, names, n_regions, label=N
         ids.append(i); msk.append(m); seg.append(s); mpos.append(p); texts_b.append(tb)
     return {"text_a": text_a, "texts_b": texts_b, "input_ids": np.stack(ids), "input_mask": np.stack(msk), "segment_ids": np.stack(seg),
             "mask_token_pos": mpos, "label": [0] if label is None else label, "q_id": int(q_id)}
+
+
+# ---- VG-CPT predicate prompts -----------------------------------------------------------------------------------------------------
+# Counterparts of ZSLVGDataset.__getitem__ (/root/reference/Oscar/oscar/datasets/vg_test_dataset.py:37-77) and FtVGDataset.__getitem__
+# (datasets/vg_cpt_dataset.py:37-101) on one row parsed by cpt_amd.io.decode_row: info["objects"] = [objs, colors, names, rel_name] with
+# objs[0] the row's one box list.  The image name ends in "_<subject box>_<object box>".  text_a: "S in c0 color is [MASK] x k a O in c1
+# color"; text_b: the box labels with the colour words in front of the pair's two "labels" (characters: see _vg_texts).  The datasets' tokenize() is ``tokenize`` above.
+VG_REL2REL = {"has": "having", "wears": "wearing", "says": "saying"}          # vg_cpt_dataset.py:40, vg_cpt.py:259
+VG_NA = {0: "irrelevant", 1: "no relation", 2: " no relation with"}          # vg_cpt_dataset.py:74: labels of the other templates
+VG_TXT_SEQ_LEN, VG_IMG_SEQ_LEN = 70, 60
+
+
+def vg_pair(img_name):
+    """The (subject, object) box indices: the last two '_'-fields of the image name."""
+    return [int(x) for x in img_name.split("_")[-2:]]
+
+
+def _vg_texts(img_name, info):
+    objs, colors, names = info["objects"][:3]
+    pair = vg_pair(img_name)
+
+    def label(i, name):
+        if i == pair[0]:
+            return colors[0] + " " + name
+        if i == pair[1]:
+            return colors[1] + " " + name
+        return name
+    # quirk kept: the datasets join the box classes into ONE string and then enumerate it, so the "labels" are its characters and the
+    # colour words go in front of characters pair[0] and pair[1] (vg_test_dataset.py:43, 92-93)
+    od_labels = " ".join(label(i, ch) for i, ch in enumerate(" ".join(o["class"] for o in objs[0])))
+    so = [names[0] + " in {} color".format(colors[0]), names[1] + " in {} color".format(colors[1])]
+    return so, od_labels, len(objs[0])
+
+
+def _vg_sequences(tokenizer, img_name, captions, od_labels, n_regions, img_seq_len):
+    P = len(captions)
+    input_ids = np.zeros((P, VG_TXT_SEQ_LEN), dtype=np.int64)
+    segment_ids = np.zeros((P, VG_TXT_SEQ_LEN), dtype=np.int64)
+    input_mask = np.zeros((P, VG_TXT_SEQ_LEN + img_seq_len), dtype=np.int64)
+    rows = []
+    for s, (text_a, k) in enumerate(captions):
+        ids, msk, seg, _ = tokenize(tokenizer, text_a, od_labels, n_regions, max_img_seq_len=img_seq_len, max_seq_a_len=40,
+                                    max_seq_len=VG_TXT_SEQ_LEN)
+        pos = np.nonzero(ids == MASK_ID)[0]
+        if pos.size != k:
+            raise ValueError("%s: sequence %d holds %d [MASK] tokens after truncation, its template has %d" % (img_name, s, pos.size, k))
+        input_ids[s], input_mask[s], segment_ids[s] = ids, msk, seg
+        rows += [(s, int(p)) for p in pos]
+    return input_ids, input_mask, segment_ids, np.asarray(rows, dtype=np.int64).reshape(-1, 2)
+
+
+def assemble_vg_zsl(tokenizer, img_name, info, img_seq_len=VG_IMG_SEQ_LEN):
+    """ZSLVGDataset.__getitem__ for one row: 6 sequences, "S ... [MASK] x k a O" for k = 1, 2, 3, then S and O swapped.
+    Returns int64 arrays input_ids (6, 70), input_mask (6, 70 + img_seq_len), segment_ids (6, 70), mask_token_pos (12, 2) =
+    (sequence, position) of every [MASK] row (sequence s holds s % 3 + 1: scoring.vg_slot_rows_from's layout), and pair / colors.
+    Raises ValueError naming the row for more than img_seq_len regions (the reference tokenizes the untruncated features: its mask
+    grows past 70 + img_seq_len and the model call fails) and when truncation would cut a [MASK] out of a caption."""
+    so, od_labels, n = _vg_texts(img_name, info)
+    if n > img_seq_len:
+        raise ValueError("%s: %d regions exceed img_seq_len %d (the zero-shot mask would outgrow the feature tensor)" % (img_name, n, img_seq_len))
+    caption, re_caption = so[0] + " is {} a " + so[1], so[1] + " is {} a " + so[0]
+    caps = [(caption.format(" [MASK]" * k), k) for k in (1, 2, 3)] + [(re_caption.format(" [MASK]" * k), k) for k in (1, 2, 3)]
+    ids, msk, seg, rows = _vg_sequences(tokenizer, img_name, caps, od_labels, n, img_seq_len)
+    return {"img_name": img_name, "input_ids": ids, "input_mask": msk, "segment_ids": seg, "mask_token_pos": rows,
+            "pair": vg_pair(img_name), "colors": list(info["objects"][1])}
+
+
+def vg_relation_ids(tokenizer, rel_name):
+    """The word-piece ids of a predicate, rel2rel applied (has -> having, wears -> wearing, says -> saying)."""
+    return tokenizer.convert_tokens_to_ids(tokenizer.tokenize(VG_REL2REL.get(rel_name, rel_name)))
+
+
+def assemble_vg_train(tokenizer, img_name, info, img_seq_len=VG_IMG_SEQ_LEN):
+    """FtVGDataset.__getitem__ for one row: 3 sequences (k = 1, 2, 3 [MASK]s, subject first) and per [MASK] row its label -- the
+    predicate's word-pieces on the template whose k is their count, VG_NA's words on the other two.  Regions beyond img_seq_len are cut
+    before tokenizing, as the dataset cuts them.  Returns input_ids (3, 70), input_mask (3, 70 + img_seq_len), segment_ids (3, 70),
+    mask_token_pos (6, 2) (sequence, position), row_labels (6,) and rel_label (the predicate's ids).  Raises ValueError for a predicate
+    of 0 or more than 3 word-pieces, a "no relation" label whose piece count differs from its template's, and a cut [MASK]."""
+    so, od_labels, n = _vg_texts(img_name, info)
+    rel = vg_relation_ids(tokenizer, info["objects"][3])
+    if not 1 <= len(rel) <= 3:
+        raise ValueError("%s: predicate %r has %d word-pieces; the templates hold 1 to 3 [MASK]s" % (img_name, info["objects"][3], len(rel)))
+    labels = [tokenizer.convert_tokens_to_ids(tokenizer.tokenize(VG_NA[i])) for i in range(3)]
+    labels[len(rel) - 1] = rel
+    for k, lab in enumerate(labels, 1):
+        if len(lab) != k:
+            raise ValueError("%s: label %r of the %d-[MASK] template has %d word-pieces" % (img_name, lab, k, len(lab)))
+    template = so[0] + " is {} a " + so[1]
+    caps = [(template.format(" [MASK]" * k), k) for k in (1, 2, 3)]
+    ids, msk, seg, rows = _vg_sequences(tokenizer, img_name, caps, od_labels, min(n, img_seq_len), img_seq_len)
+    return {"img_name": img_name, "input_ids": ids, "input_mask": msk, "segment_ids": seg, "mask_token_pos": rows,
+            "row_labels": np.asarray([t for lab in labels for t in lab], dtype=np.int64), "rel_label": list(rel),
+            "pair": vg_pair(img_name), "colors": list(info["objects"][1])}
+
+
+def vg_predicates(idx_to_predicate, tokenizer):
+    """vg_cpt.py:260-262: {predicate index: word-piece ids} from the vocabulary file's idx_to_predicate (rel2rel applied), ready for
+    scoring.vg_candidates."""
+    return {int(idx): vg_relation_ids(tokenizer, pred) for idx, pred in idx_to_predicate.items()}

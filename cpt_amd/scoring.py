@@ -5,6 +5,7 @@ Oscar/oscar/fewshot/refcoco_cpt.py:277-295 (colour logit / "none" logit) and
 Oscar/oscar/utils/iou.py:1-12.  Host-side: the inputs are the (B, V) [MASK]-row logits the HIP path
 returns; only B x n_colour values are touched, and torch.argmax's first-max tie-break is kept.
 """
+import numpy as np
 import torch
 
 
@@ -210,3 +211,182 @@ def vg_predicate_scores(model, input_ids, segment_ids, attention_mask, img_feats
     n_pairs = B // 6
     sc = mean_logprob_scores_device(out["logits"], out["lse"], slot_row, cand_cols, cand_len)
     return sc.view(n_pairs, 2, -1)
+
+
+# ---- VG Recall@K / mean Recall@K (Oscar/oscar/utils/vg_eval.py eval_vg) ----------------------------------------------------------
+# Prediction keys are "<image>.jpg_<subject>_<object>" (vg_cpt.py:211-214); eval_vg groups them by image in dict order, adds an all-zero
+# dummy row for every ground-truth image without one, ranks each image's pairs by the score of their best predicate (index >= 1), and
+# counts a ground-truth triplet (s, o, r) as hit@K when (s, o, r) is among the top K.  The device form ranks once (cpt_vg_recall_ranks);
+# hit@K = rank < K for every K, reduced in float64 on the device.
+VG_MODES = (20, 50, 100)
+
+
+def reverse_imkey(key):
+    """vg_cpt.py:211-214: the key of the same image with subject and object swapped."""
+    s, o = [int(x) for x in key.split("_")[-2:]]
+    return key.split(".jpg")[0] + ".jpg" + "_" + str(o) + "_" + str(s)
+
+
+def _imkey_split(key):
+    return key.split(".jpg")[0] + ".jpg", [int(x) for x in key.split("_")[-2:]]
+
+
+def vg_eval_table(keys, gts, n_slots=51):
+    """eval_vg's bookkeeping as CSR tables, once per split.  keys: the prediction key of every score row, in the order the rows were
+    written (predictions[k] = v: a repeated key keeps its first position and takes the LAST row); gts: the ground-truth list of eval_vg
+    (dicts with "img_path" and "relations" (n, 3) = subject, object, predicate).  Images come in ground-truth order; an image without a
+    prediction gets the reference's dummy candidate (pair (0, 0), all-zero row: relation 1 at score 0).  Raises ValueError where
+    eval_vg fails: a predicted image absent from the ground truth, an image without ground-truth relations, a predicate >= n_slots
+    (and, refused outright, a negative predicate or a repeated ground-truth image).
+    Returns a dict of int32 CPU tensors: cand_off (n_img + 1), cand (n_cand, 3) = (s, o, row; -1 = dummy), gt_off (n_img + 1),
+    gt (n_gt, 3), gt_img (n_gt,), plus images, n_rows = len(keys), n_slots."""
+    where = {}
+    for i, k in enumerate(keys):
+        where[k] = i                                   # dict assignment: first position, last value
+    by_img = {}
+    for k, row in where.items():
+        img, pair = _imkey_split(k)
+        by_img.setdefault(img, []).append((pair[0], pair[1], row))
+    images = [str(g["img_path"]) for g in gts]
+    if len(set(images)) != len(images):
+        raise ValueError("cpt_amd: the ground truth lists an image twice (eval_vg's length assert fails)")
+    known = set(images)
+    extra = [img for img in by_img if img not in known]
+    if extra:
+        raise ValueError("cpt_amd: predicted image %r is absent from the ground truth (eval_vg's length assert fails)" % extra[0])
+    cand_off, cand, gt_off, gt, gt_img = [0], [], [0], [], []
+    for gi, g in enumerate(gts):
+        img = images[gi]
+        cand += by_img.get(img, [(0, 0, -1)])
+        cand_off.append(len(cand))
+        rel = torch.as_tensor(g["relations"]).long().reshape(-1, 3)
+        if rel.size(0) == 0:
+            raise ValueError("cpt_amd: image %r has no ground-truth relation (eval_vg divides 0 by 0.0)" % img)
+        if int(rel[:, 2].max()) >= n_slots or int(rel[:, 2].min()) < 0:
+            raise ValueError("cpt_amd: image %r has a ground-truth predicate outside [0, %d)" % (img, n_slots))
+        gt.append(rel)
+        gt_img += [gi] * rel.size(0)
+        gt_off.append(gt_off[-1] + rel.size(0))
+    i32 = torch.int32
+    return {"cand_off": torch.tensor(cand_off, dtype=i32), "cand": torch.tensor(cand, dtype=i32).view(-1, 3),
+            "gt_off": torch.tensor(gt_off, dtype=i32), "gt": torch.cat(gt).to(i32), "gt_img": torch.tensor(gt_img, dtype=torch.int64),
+            "images": images, "n_rows": len(keys), "n_slots": int(n_slots)}
+
+
+def vg_recall_ranks_device(scores, table):
+    """cpt_vg_recall_ranks, one launch: scores (n_rows, C) or (pairs, 2, C) on the GPU, rows in the order of vg_eval_table's keys.
+    Returns (n_gt,) int32 ranks on the device: INT32_MAX where the triplet is not predicted, hit@K = rank < K."""
+    from . import _lib as L
+    if not scores.is_cuda:
+        raise RuntimeError("cpt_amd: vg_recall_ranks_device needs the scores on the GPU (no CPU fallback)")
+    dev = scores.device
+    sc = scores.reshape(-1, scores.size(-1)).contiguous().float()
+    if sc.size(0) != table["n_rows"]:
+        raise ValueError("cpt_amd: %d score rows for %d prediction keys" % (sc.size(0), table["n_rows"]))
+    dt = table.get("_dev")
+    if dt is None or dt[0] != dev:
+        ws_bytes = int(L.lib().cpt_vg_recall_workspace_bytes(table["cand_off"].data_ptr(), len(table["images"])))
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        dt = (dev, {k: table[k].to(dev).contiguous() for k in ("cand_off", "cand", "gt_off", "gt", "gt_img")}, ws, ws_bytes)
+        table["_dev"] = dt
+    _, t, ws, ws_bytes = dt
+    n_gt = t["gt"].size(0)
+    out = torch.empty(n_gt, dtype=torch.int32, device=dev)
+    L.check(L.lib().cpt_vg_recall_ranks(sc.data_ptr(), sc.size(0), sc.size(1), t["cand_off"].data_ptr(), t["cand"].data_ptr(), t["cand"].size(0),
+                                        t["gt_off"].data_ptr(), t["gt"].data_ptr(), n_gt, len(table["images"]), out.data_ptr(),
+                                        ws.data_ptr() if ws_bytes else None, ws_bytes, L.stream_ptr()), "cpt_vg_recall_ranks")
+    return out
+
+
+def vg_recall_from_ranks(ranks, table, modes=VG_MODES):
+    """R@K and mR@K from per-triplet ranks, in float64 torch on the ranks' device.  R@K: mean over images of hits / |gt|.  mR@K: mean over
+    predicates 1..n_slots-1 of the mean over images holding the predicate of that image's recall of it (0 for a predicate never seen;
+    the reference's range(51) makes n_slots = 51 divide by 50 whatever the vocabulary)."""
+    dev = ranks.device
+    n_img, S = len(table["images"]), table["n_slots"]
+    gimg = table["gt_img"].to(dev)
+    rel = table["gt"][:, 2].to(device=dev, dtype=torch.int64)
+    cell = gimg * S + rel
+    f64 = torch.float64
+    n_per_img = torch.zeros(n_img, dtype=f64, device=dev).index_add_(0, gimg, torch.ones_like(gimg, dtype=f64))
+    cnt = torch.zeros(n_img * S, dtype=f64, device=dev).index_add_(0, cell, torch.ones_like(cell, dtype=f64)).view(n_img, S)
+    seen = cnt > 0
+    n_seen = seen.sum(0).to(f64)
+    recall, mrecall = {}, {}
+    for K in modes:
+        hit = (ranks.long() < K).to(f64)
+        per_img = torch.zeros(n_img, dtype=f64, device=dev).index_add_(0, gimg, hit) / n_per_img
+        recall[K] = per_img.mean()
+        hc = torch.zeros(n_img * S, dtype=f64, device=dev).index_add_(0, cell, hit).view(n_img, S)
+        ratio = torch.where(seen, hc / cnt.clamp_min(1), torch.zeros_like(hc)).sum(0)
+        per_pred = torch.where(n_seen > 0, ratio / n_seen.clamp_min(1), torch.zeros_like(ratio))
+        mrecall[K] = per_pred[1:].mean()
+    return {"recall": {K: float(v) for K, v in recall.items()}, "mrecall": {K: float(v) for K, v in mrecall.items()}}
+
+
+def vg_recall_device(scores, table, modes=VG_MODES):
+    """Recall@K and mean Recall@K of a split on the device: cpt_vg_recall_ranks, then the float64 reductions.  Only the 2 x len(modes)
+    results leave the GPU.  Returns {"recall": {K: R@K}, "mrecall": {K: mR@K}, "ranks": (n_gt,) int32 on the device}."""
+    ranks = vg_recall_ranks_device(scores, table)
+    out = vg_recall_from_ranks(ranks, table, modes)
+    out["ranks"] = ranks
+    return out
+
+
+def format_vg_recall(result):
+    """The two-line string eval_vg returns (R@20/50/100, then mR@20/50/100)."""
+    r, m = result["recall"], result["mrecall"]
+    rst = "R@20: {:.4f}\tR@50: {:.4f}\tR@100: {:.4f}".format(r[20], r[50], r[100]) + "\n"
+    rst += "mR@20: {:.4f}\tmR@50: {:.4f}\tmR@100: {:.4f}".format(m[20], m[50], m[100]) + "\n"
+    return rst
+
+
+def eval_vg_reference(predictions, gts, modes=VG_MODES, n_slots=51):
+    """Torch restatement of eval_vg on the host, no device call: predictions {key: (C,) scores} in dict order, gts as vg_eval_table.  The
+    image loop, argmax over predicates 1.., descending sort (stable: ties keep candidate order, NaN first), top-K matching, and the
+    per-predicate means, written as the reference writes them but in float64.  Returns {"recall", "mrecall", "ranks" (n_gt,) int64
+    (INT32_MAX = not predicted; triplets in ground-truth order), "string"}."""
+    new_preds = {}
+    for k, v in predictions.items():
+        img, pair = _imkey_split(k)
+        new_preds.setdefault(img, []).append((pair, v))
+    C = next(iter(predictions.values())).numel() if predictions else n_slots
+    for g in gts:
+        if g["img_path"] not in new_preds:
+            new_preds[g["img_path"]] = [([0, 0], torch.zeros(C, dtype=torch.float))]
+    gts = [g for g in gts if g["img_path"] in new_preds]
+    if len(new_preds) != len(gts):
+        raise ValueError("cpt_amd: %d predicted images, %d ground-truth images" % (len(new_preds), len(gts)))
+    big = 2 ** 31 - 1
+    recall = {K: [] for K in modes}
+    mrecall = {K: [[] for _ in range(n_slots)] for K in modes}
+    all_ranks = []
+    for g in gts:
+        p_list = new_preds[g["img_path"]]
+        pairs = torch.tensor([p for p, _ in p_list], dtype=torch.int64)
+        prds = torch.stack([v.float().cpu() for _, v in p_list], 0)
+        rels = prds[:, 1:].argmax(1) + 1
+        scores = prds[torch.arange(len(prds)), rels]
+        idxs = torch.sort(scores, descending=True, stable=True).indices
+        trip = torch.cat([pairs[idxs], rels[idxs][:, None]], -1)
+        gt_rels = torch.as_tensor(g["relations"]).long().reshape(-1, 3)
+        if gt_rels.size(0) == 0:
+            raise ValueError("cpt_amd: image %r has no ground-truth relation" % g["img_path"])
+        eq = (gt_rels[:, None, :] == trip[None, :, :]).all(2)                  # (n_gt, n_cand) in rank order
+        first = torch.where(eq.any(1), eq.float().argmax(1), torch.full((gt_rels.size(0),), big, dtype=torch.int64))
+        all_ranks.append(first)
+        for K in modes:
+            rcl = first < K
+            recall[K].append(float(rcl.sum()) / float(len(gt_rels)))
+            tot, hit = {}, {}
+            for r, c in zip(gt_rels[:, 2].tolist(), rcl.tolist()):
+                tot[r] = tot.get(r, 0) + 1
+                hit[r] = hit.get(r, 0) + int(c)
+            for r in hit:
+                mrecall[K][r].append(hit[r] / tot[r])
+    out = {"recall": {K: float(np.mean(v)) for K, v in recall.items()},
+           "mrecall": {K: float(np.mean([np.mean(v) if len(v) > 0 else 0 for v in vl[1:]])) for K, vl in mrecall.items()},
+           "ranks": torch.cat(all_ranks) if all_ranks else torch.zeros(0, dtype=torch.int64)}
+    if set(VG_MODES) <= set(modes):
+        out["string"] = format_vg_recall(out)
+    return out

@@ -224,6 +224,22 @@ int cpt_model_fwd_rows(const cpt_model* m, const cpt_batch* b, const int64_t* co
 int cpt_mean_logprob_scores(const float* logits, int n_cols, int n_rows, const float* row_lse, const int32_t* slot_row, int G, int K,
                             const int32_t* cand_cols, const int32_t* cand_len, int C, float* out, void* stream);
 
+/* VG Recall@K ranks (Oscar/oscar/utils/vg_eval.py eval_vg), one launch for a whole split; added beside ABI 8, no struct changed.
+ * Images come as CSR tables (int32, device):
+ *   cand_off [n_img + 1], cand [n_cand][3] = (subject, object, score row): the image's candidates in the reference's dict order;
+ *     score row -1 (or any row outside [0, n_rows)) is the all-zero dummy row of an image without predictions;
+ *   gt_off [n_img + 1], gt [n_gt][3] = (subject, object, predicate): the image's ground-truth triplets.
+ *   scores [n_rows][C] fp32 (device, C >= 2).
+ * Per candidate rel = argmax(row[1:]) + 1 (first maximum; NaN counts as the maximum) and score = row[rel]; per image the candidates
+ * are ranked by score, descending, ties by candidate order, NaN first (a stable torch.sort(descending=True)).
+ * out_rank [n_gt]: the rank of the candidate with the triplet's (subject, object) whose rel equals its predicate, INT32_MAX if there is
+ * none (hit@K = rank < K); -1 if the image's offsets are inconsistent or the workspace is too small for it.
+ * Images with more candidates than the LDS tile are ranked through `workspace`: cpt_vg_recall_workspace_bytes sizes it from the HOST
+ * copy of cand_off (0 when every image fits the tile; workspace may then be NULL). */
+size_t cpt_vg_recall_workspace_bytes(const int32_t* cand_off, int n_img);
+int cpt_vg_recall_ranks(const float* scores, int n_rows, int C, const int32_t* cand_off, const int32_t* cand, int n_cand, const int32_t* gt_off,
+                        const int32_t* gt, int n_gt, int n_img, int32_t* out_rank, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Few-shot training step (Oscar/oscar/fewshot/refcoco_cpt.py:231-249): forward that keeps the
  * activations, backward into caller-owned fp32 gradient tensors laid out like the parameters,
