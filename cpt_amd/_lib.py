@@ -73,6 +73,11 @@ class Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("seq", "pooled", "logits", "loss", "rel", "loss_mean", "logit_cols")] + [("n_logit_cols", C.c_int64)]
 
 
+class Rel2(C.Structure):
+    """cpt_rel2: the second relation head of VCR Q->AR (rows [B0, B) of the batch)."""
+    _fields_ = [("B0", C.c_int32)] + [(n, C.c_void_p) for n in ("w_rel1", "b_rel1", "g_w_rel1", "g_b_rel1", "score", "labels_host")]
+
+
 _SIGS = {
     "cpt_version": (C.c_int, []),
     "cpt_last_error": (C.c_char_p, []),
@@ -84,6 +89,14 @@ _SIGS = {
     "cpt_mean_logprob_scores": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
     "cpt_vg_recall_workspace_bytes": (C.c_size_t, [vp, C.c_int]),
     "cpt_vg_recall_ranks": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.c_size_t, vp]),
+    "cpt_rel2_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "cpt_rel2_scores": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+    "cpt_vcr_qar_choose": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "cpt_train_fwd_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(Batch), C.POINTER(Outputs), vp, C.c_size_t, vp, BUCKET_CB, vp,
+                                     C.POINTER(Dropout)]),
+    "cpt_train_bwd_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(Batch), C.POINTER(ModelGrads), C.c_float, vp, vp, C.c_size_t, vp,
+                                     BUCKET_CB, vp, C.POINTER(Dropout)]),
+    "cpt_train_zero_grads_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(ModelGrads), C.c_int, vp]),
     "cpt_train_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int, C.c_int]),
     "cpt_train_workspace_bytes_rows": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int, C.c_int, C.c_int]),
     "cpt_train_fwd": (C.c_int, [C.POINTER(Model), C.POINTER(Batch), C.POINTER(Outputs), vp, C.c_size_t, vp]),

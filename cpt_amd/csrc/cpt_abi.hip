@@ -992,3 +992,49 @@ int cpt_vg_recall_ranks(const float* scores, int n_rows, int C, const int32_t* c
 }
 
 }  // extern "C"
+
+// ---- VCR Q->AR: the two relation heads on pooled rows, and the Q->AR choice (qar_head.hip) ----
+extern "C" {
+
+size_t cpt_rel2_workspace_bytes(int B) {
+    if (B <= 0) return 0;
+    return 256 + ((size_t)B * 4 + 255) / 256 * 256;      // [0, 256): the finish ticket; then B row losses
+}
+
+int cpt_rel2_scores(int dtype, const float* pooled, int B, int H, int n_rel, int B0, const void* w0, const float* b0, const void* w1, const float* b1,
+                    const int64_t* labels, const int64_t* labels_host, float* rel, float* score, float* loss, float* loss_mean, float* dlogits,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    if (!pooled || !rel) return fail(CPT_ERR_NULL, "cpt_rel2_scores: null argument");
+    if (B <= 0 || H <= 0 || n_rel < 1 || n_rel > 64) return fail(CPT_ERR_SHAPE, "cpt_rel2_scores: B %d H %d n_rel %d (1 <= n_rel <= 64)", B, H, n_rel);
+    if (B0 < 0 || B0 > B) return fail(CPT_ERR_SHAPE, "cpt_rel2_scores: B0 %d outside [0, B = %d]", B0, B);
+    if ((B0 > 0 && (!w0 || !b0)) || (B0 < B && (!w1 || !b1))) return fail(CPT_ERR_NULL, "cpt_rel2_scores: a head with rows has no weights");
+    if (score && n_rel < 2) return fail(CPT_ERR_SHAPE, "cpt_rel2_scores: the choice score needs n_rel >= 2");
+    if (dtype < CPT_F32 || dtype > CPT_BF16X3_MASTERS) return fail(CPT_ERR_DTYPE, "cpt_rel2_scores: dtype %d", dtype);
+    hipStream_t s = (hipStream_t)stream;
+    float* rowloss = nullptr;
+    unsigned* ticket = nullptr;
+    float* dl = nullptr;
+    if (labels) {
+        if (!workspace || workspace_bytes < cpt_rel2_workspace_bytes(B)) return fail(CPT_ERR_WORKSPACE, "cpt_rel2_scores: workspace %zu < %zu bytes", workspace_bytes, cpt_rel2_workspace_bytes(B));
+        if (!dlogits) return fail(CPT_ERR_NULL, "cpt_rel2_scores: labels need dlogits [B][n_rel] (the launch's per-row gradient)");
+        if (int rc = cpt::rel2_check_labels(labels, labels_host, B, n_rel, "cpt_rel2_scores", s)) return rc;
+        ticket = (unsigned*)workspace;
+        rowloss = (float*)((char*)workspace + 256);
+        dl = dlogits;
+    }
+    // (without labels the head pointers of an empty group are never read: pass the other head's so the kernel sees valid pointers)
+    const void* w0_ = B0 > 0 ? w0 : w1; const float* b0_ = B0 > 0 ? b0 : b1;
+    const void* w1_ = B0 < B ? w1 : w0; const float* b1_ = B0 < B ? b1 : b0;
+    return check_launch(cpt::rel2_fwd(dtype == CPT_BF16, pooled, B, H, n_rel, B0, w0_, b0_, w1_, b1_, labels, rel, score, dl, rowloss, ticket, loss,
+                                      loss_mean, s), "cpt_rel2_scores");
+}
+
+int cpt_vcr_qar_choose(const float* q_a, const float* qa_r, int n_q, int n_ans, int n_rats, const int64_t* ans_label, const int64_t* rat_label,
+                       int64_t* preds, uint8_t* flags, int32_t* counts, void* stream) {
+    if (!q_a || !qa_r || !ans_label || !rat_label || !preds || !flags) return fail(CPT_ERR_NULL, "cpt_vcr_qar_choose: null argument");
+    if (n_q <= 0 || n_ans <= 0 || n_rats <= 0) return fail(CPT_ERR_SHAPE, "cpt_vcr_qar_choose: n_q %d n_ans %d n_rats %d", n_q, n_ans, n_rats);
+    return check_launch(cpt::qar_choose(q_a, qa_r, n_q, n_ans, n_rats, ans_label, rat_label, preds, flags, counts, (hipStream_t)stream),
+                        "cpt_vcr_qar_choose");
+}
+
+}  // extern "C"

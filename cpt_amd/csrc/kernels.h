@@ -300,5 +300,14 @@ int vg_recall(const float* scores, int n_rows, int C, const int32_t* cand_off, c
               const int32_t* gt, int n_gt, int n_img, int32_t* out_rank, void* ws, size_t ws_bytes, hipStream_t s);
 size_t vg_recall_ws_bytes(long long n_big);
 int vg_recall_tile();
+// qar_head.hip: the two relation heads of VCR Q->AR on one batch (cpt_rel2_scores, cpt_train_*_rel2, cpt_vcr_qar_choose)
+int rel2_fwd(int lp, const float* pooled, int B, int H, int n_rel, int B0, const void* w0, const float* b0, const void* w1, const float* b1,
+             const int64_t* labels, float* rel, float* score, float* dlogits, float* rowloss, unsigned* ticket, float* loss2, float* loss_mean,
+             hipStream_t s);
+int rel2_bwd(int lp, const float* pooled, int B, int H, int n_rel, int B0, const void* w0, const void* w1, const float* dlogits, float scale,
+             const float* scale_dev, float* dpooled, float* gw0, float* gb0, float* gw1, float* gb1, hipStream_t s);
+int rel2_check_labels(const int64_t* labels, const int64_t* labels_host, int B, int n_rel, const char* who, hipStream_t s);   // host: [-1, n_rel)
+int qar_choose(const float* q_a, const float* qa_r, int n_q, int n_ans, int n_rats, const int64_t* ans_label, const int64_t* rat_label,
+               int64_t* preds, uint8_t* flags, int* counts, hipStream_t s);
 
 }  // namespace cpt

@@ -191,6 +191,19 @@ int check_drop(const cpt_dropout* d, const char* who) {
     return CPT_OK;
 }
 
+// VCR Q->AR second head: B0, n_rel, head 1's weights and the label range ([-1, n_rel): from the host copy when given, else read back once)
+int check_rel2(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, const char* who, void* stream, bool labels_too = true) {
+    const int n_rel = m->dims.n_rel;
+    if (!x->w_rel1 || !x->b_rel1 || !m->w_rel || !m->b_rel) return abi_fail(CPT_ERR_NULL, "%s: both relation heads (w_rel / b_rel, w_rel1 / b_rel1) are required", who);
+    if (n_rel < 1 || n_rel > 64) return abi_fail(CPT_ERR_SHAPE, "%s: n_rel %d outside [1, 64]", who, n_rel);
+    if (x->score && n_rel < 2) return abi_fail(CPT_ERR_SHAPE, "%s: the choice score needs n_rel >= 2", who);
+    if (x->B0 < 0 || x->B0 > b->B) return abi_fail(CPT_ERR_SHAPE, "%s: B0 %d outside [0, B = %d]", who, x->B0, b->B);
+    if (b->n_rows != 0) return abi_fail(CPT_ERR_SHAPE, "%s: label grids (n_rows) belong to the MLM head", who);
+    if (!labels_too) return CPT_OK;
+    if (!b->labels) return abi_fail(CPT_ERR_NULL, "%s: labels are required", who);
+    return cpt::rel2_check_labels(b->labels, x->labels_host, b->B, n_rel, who, (hipStream_t)stream);
+}
+
 // the pruned last layer (g_train_tail): bf16 step, one head row per sequence (no label grid), tile-aligned hidden sizes, 2-D mask
 bool train_tail_on(const cpt_dims& d, const cpt_batch* b) {
     return g_train_tail && g_wgrad_tn && d.dtype == CPT_BF16 && b->n_rows == 0 && d.layers >= 1 && d.hidden % 192 == 0 && d.inter % 192 == 0 &&
@@ -244,8 +257,9 @@ static inline bool train_x3_attention(const cpt_dims& d, int L, int m3d) {
     return d.dtype == CPT_BF16X3_MASTERS && !m3d && cpt::attention_x3_supported(L) && cpt::attention_bwd_x3_supported(L, m3d);
 }
 
-int cpt_train_fwd_ex(const cpt_model* m, const cpt_batch* b, const cpt_outputs* o, void* workspace,
-                     size_t workspace_bytes, void* stream, cpt_bucket_fn before_bucket, void* user, const cpt_dropout* drop) {
+// x: the second relation head of VCR Q->AR (cpt_train_fwd_rel2), NULL for every other model
+static int train_fwd_impl(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, const cpt_outputs* o, void* workspace,
+                          size_t workspace_bytes, void* stream, cpt_bucket_fn before_bucket, void* user, const cpt_dropout* drop) {
     if (!m || !b || !o || !workspace) return abi_fail(CPT_ERR_NULL, "cpt_train_fwd: null argument");
     if (int rcd = check_drop(drop, "cpt_train_fwd")) return rcd;
     const bool ph = drop && drop->p_hidden > 0.f, pa = drop && drop->p_attn > 0.f;
@@ -256,6 +270,10 @@ int cpt_train_fwd_ex(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
     const bool nsp = !m->w_tr && !m->w_dec;
     if (nsp && b->n_rows > 0) return abi_fail(CPT_ERR_SHAPE, "cpt_train_fwd: label grids (n_rows) belong to the MLM head, not the NSP head");
     if (!o->loss || (nsp ? !o->rel : !o->logits)) return abi_fail(CPT_ERR_NULL, "cpt_train_fwd: loss and logits (NSP head: rel) outputs are required");
+    if (x) {
+        if (int rx = check_rel2(m, x, b, "cpt_train_fwd_rel2", stream)) return rx;
+        if (!nsp) return abi_fail(CPT_ERR_NULL, "cpt_train_fwd_rel2: the model needs the pooler and head 0 (w_pool, w_rel) and no MLM head");
+    }
     hipStream_t s = (hipStream_t)stream;
     const bool x3 = d.dtype == CPT_BF16X3_MASTERS;
     const int B = b->B, Lt = b->Lt, Li = b->Li, L = Lt + Li, M = B * L, H = d.hidden, I = d.inter, dt = x3 ? CPT_F32 : d.dtype;
@@ -436,6 +454,14 @@ int cpt_train_fwd_ex(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
         // NSPCPT: pooled = tanh([CLS] W_pool^T + b_pool) (kept in `uh`), rel = pooled W_rel^T + b_rel, CE over n_rel classes
         if (!tail) TRY(cpt::gather_rows(ws + w.xout, dt, nullptr, rows, B, L, H, s), "gather([CLS])");
         TRY(gm(CPT_EPI_TANH, rows, H, m->w_pool, H, m->b_pool, nullptr, 0, uh, CPT_F32, H, B, H, H, s), "gemm(pooler)");
+        if (x) {
+            // VCR Q->AR: both heads and the grouped cross entropy in one launch on the fp32 pooled rows (row losses behind the B x n_rel
+            // dlogits block of the workspace; the embedding launch above cleared the finish ticket)
+            float* dlg = (float*)(ws + w.dlogits);
+            TRY(cpt::rel2_fwd(dt == CPT_BF16, uh, B, H, d.n_rel, x->B0, m->w_rel, m->b_rel, x->w_rel1, x->b_rel1, b->labels, o->rel, x->score, dlg,
+                              dlg + (size_t)B * d.n_rel, ce_ticket, o->loss, o->loss_mean, s), "rel2_fwd(two heads + grouped cross entropy)");
+            return CPT_OK;
+        }
         const void* pin = uh;
         if (dt == CPT_BF16) {
             TRY(cpt::layernorm_rows(uh, nullptr, nullptr, 0.f, nullptr, t2, dt, B, H, B, 0, 0, s), "cast(pooled)");
@@ -462,8 +488,8 @@ int cpt_train_bwd(const cpt_model* m, const cpt_batch* b, const cpt_model_grads*
     return cpt_train_bwd_ex(m, b, g, loss_scale, nullptr, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr);
 }
 
-int cpt_train_bwd_ex(const cpt_model* m, const cpt_batch* b, const cpt_model_grads* g, float loss_scale, const float* loss_scale_dev,
-                     void* workspace, size_t workspace_bytes, void* stream, cpt_bucket_fn grads_ready, void* user, const cpt_dropout* drop) {
+static int train_bwd_impl(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, const cpt_model_grads* g, float loss_scale, const float* loss_scale_dev,
+                          void* workspace, size_t workspace_bytes, void* stream, cpt_bucket_fn grads_ready, void* user, const cpt_dropout* drop) {
     if (!m || !b || !g || !workspace) return abi_fail(CPT_ERR_NULL, "cpt_train_bwd: null argument");
     if (int rcd = check_drop(drop, "cpt_train_bwd")) return rcd;
     const bool ph = drop && drop->p_hidden > 0.f, pa = drop && drop->p_attn > 0.f;
@@ -563,16 +589,24 @@ int cpt_train_bwd_ex(const cpt_model* m, const cpt_batch* b, const cpt_model_gra
     const bool nsp = !m->w_tr && !m->w_dec;
     const bool tail = train_tail_on(d, b) && !(b->mask_3d && b->attn_mask);      // the forward's pruned last layer (same predicate)
     const int Rh = (!nsp && b->n_rows > 0) ? b->n_rows : B;      // head rows (see cpt_train_fwd)
+    if (x && !nsp) return abi_fail(CPT_ERR_NULL, "cpt_train_bwd_rel2: the model needs the pooler and head 0 (w_pool, w_rel) and no MLM head");
     if (nsp) {
         if (!g->w_pool || !g->b_pool || !g->w_rel || !g->b_rel) return abi_fail(CPT_ERR_NULL, "cpt_train_bwd: NSP head needs the w_pool / b_pool / w_rel / b_rel gradient tensors");
         const int NR = d.n_rel, NRp = 64;
         const float* pooled = (const float*)(ws + w.uh);
+        if (x) {
+            // VCR Q->AR: dpooled and both heads' gradients in one launch (fixed-order sums, no float atomics); the pooler chain below is unchanged
+            if (!x->g_w_rel1 || !x->g_b_rel1) return abi_fail(CPT_ERR_NULL, "cpt_train_bwd_rel2: head 1 needs the g_w_rel1 / g_b_rel1 gradient tensors");
+            TRY(cpt::rel2_bwd(dt == CPT_BF16, pooled, B, H, NR, x->B0, m->w_rel, x->w_rel1, (const float*)(ws + w.dlogits), loss_scale, loss_scale_dev,
+                              dt2, g->w_rel, g->b_rel, x->g_w_rel1, x->g_b_rel1, s), "rel2_bwd(two heads)");
+        } else {
         const void* pin = dt == CPT_BF16 ? (const void*)(ws + w.t2) : (const void*)pooled;
         TRY(cpt::scale_cast((const float*)(ws + w.dlogits), (const float*)(ws + w.loss), loss_scale, loss_scale_dev, dl_lp, dt, B, NR, NRp, s, g->b_rel), "scale(drel) + colsum(cls.bias)");
         rc = dgrad(dl_lp, NRp, NRp, m->w_rel, H, NR, H, B, nullptr, dt2, CPT_F32, "dgrad(seq_relationship)");
         if (rc) return rc;
         rc = wgrad(dl_lp, dt, NRp, NR, pin, H, H, B, Bp, g->w_rel, H, "wgrad(seq_relationship)");
         if (rc) return rc;
+        }
         TRY(cpt::tanh_bwd(dt2, pooled, duh, dt == CPT_BF16 ? duh_lp : nullptr, dt, (size_t)B * H, s), "tanh_bwd(pooler)");
         const void* dpo = dt == CPT_BF16 ? (const void*)duh_lp : (const void*)duh;
         TRY(cpt::colsum(duh, CPT_F32, H, g->b_pool, B, H, s), "colsum(pooler bias)");
@@ -821,7 +855,7 @@ int cpt_train_bwd_ex(const cpt_model* m, const cpt_batch* b, const cpt_model_gra
 // What cpt_train_bwd needs cleared, in one launch (+ one memset for a table the chosen head does not overwrite): Linear weight
 // gradients are WRITTEN by their GEMMs (and the tied word-embedding table by the decoder's), so only the vectors and small tables
 // that take atomic adds are cleared -- 0.3 MB instead of the 447 MB of a whole-buffer fill per step.
-int cpt_train_zero_grads(const cpt_model* m, const cpt_model_grads* g, int Li, void* stream) {
+static int zero_grads_impl(const cpt_model* m, const cpt_rel2* x, const cpt_model_grads* g, int Li, void* stream) {
     if (!m || !g || !g->layers) return abi_fail(CPT_ERR_NULL, "cpt_train_zero_grads: null argument");
     const cpt_dims& d = m->dims;
     hipStream_t s = (hipStream_t)stream;
@@ -849,6 +883,7 @@ int cpt_train_zero_grads(const cpt_model* m, const cpt_model_grads* g, int Li, v
     }
     seg(g->b_tr, H); seg(g->tr_ln_g, H); seg(g->tr_ln_b, H); seg(g->b_dec, (size_t)d.vocab);
     seg(g->b_pool, H); seg(g->b_rel, (size_t)d.n_rel);
+    if (x) seg(x->g_b_rel1, (size_t)d.n_rel);
     if (ovf) return abi_fail(CPT_ERR_SHAPE, "cpt_train_zero_grads: more than %d gradient vectors (layers = %d)", cpt::ZS_MAX, d.layers);
     TRY(cpt::zero_segments(z, s), "zero_segments");
     int rc;
@@ -925,6 +960,39 @@ int cpt_adamw_ex(float* p, const float* g, float* m, float* v, const unsigned ch
     if (flags & ~(CPT_ADAMW_HF | CPT_ADAMW_NO_BIAS_CORRECTION)) return abi_fail(CPT_ERR_SHAPE, "cpt_adamw_ex: unknown flags %d", flags);
     return abi_check(cpt::adamw_flat(p, g, m, v, code, shadow_bf16, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale,
                                      (hipStream_t)stream, flags), "cpt_adamw_ex");
+}
+
+int cpt_train_fwd_ex(const cpt_model* m, const cpt_batch* b, const cpt_outputs* o, void* workspace,
+                     size_t workspace_bytes, void* stream, cpt_bucket_fn before_bucket, void* user, const cpt_dropout* drop) {
+    return train_fwd_impl(m, nullptr, b, o, workspace, workspace_bytes, stream, before_bucket, user, drop);
+}
+
+int cpt_train_bwd_ex(const cpt_model* m, const cpt_batch* b, const cpt_model_grads* g, float loss_scale, const float* loss_scale_dev,
+                     void* workspace, size_t workspace_bytes, void* stream, cpt_bucket_fn grads_ready, void* user, const cpt_dropout* drop) {
+    return train_bwd_impl(m, nullptr, b, g, loss_scale, loss_scale_dev, workspace, workspace_bytes, stream, grads_ready, user, drop);
+}
+
+int cpt_train_zero_grads(const cpt_model* m, const cpt_model_grads* g, int Li, void* stream) {
+    return zero_grads_impl(m, nullptr, g, Li, stream);
+}
+
+int cpt_train_fwd_rel2(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, const cpt_outputs* o, void* workspace, size_t workspace_bytes,
+                       void* stream, cpt_bucket_fn before_bucket, void* user, const cpt_dropout* drop) {
+    if (!x) return abi_fail(CPT_ERR_NULL, "cpt_train_fwd_rel2: the second head (x) is NULL");
+    return train_fwd_impl(m, x, b, o, workspace, workspace_bytes, stream, before_bucket, user, drop);
+}
+
+int cpt_train_bwd_rel2(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, const cpt_model_grads* g, float loss_scale,
+                       const float* loss_scale_dev, void* workspace, size_t workspace_bytes, void* stream, cpt_bucket_fn grads_ready, void* user,
+                       const cpt_dropout* drop) {
+    if (!x) return abi_fail(CPT_ERR_NULL, "cpt_train_bwd_rel2: the second head (x) is NULL");
+    if (int rx = check_rel2(m, x, b, "cpt_train_bwd_rel2", stream, false)) return rx;
+    return train_bwd_impl(m, x, b, g, loss_scale, loss_scale_dev, workspace, workspace_bytes, stream, grads_ready, user, drop);
+}
+
+int cpt_train_zero_grads_rel2(const cpt_model* m, const cpt_rel2* x, const cpt_model_grads* g, int Li, void* stream) {
+    if (!x) return abi_fail(CPT_ERR_NULL, "cpt_train_zero_grads_rel2: the second head (x) is NULL");
+    return zero_grads_impl(m, x, g, Li, stream);
 }
 
 }  // extern "C"

@@ -190,3 +190,105 @@ def train_vg_batch(model, optimizer, batches, opts, device, global_step=0):
         global_step += 1
         losses.append(loss.detach())
     return global_step, losses
+
+
+# ---- VCR Q->AR (Oscar/oscar/fewshot/vcr_qar_nsp_cpt.py; launched by cmds/vcr/qar_cpt_fsl.sh) ----------------------------------------------
+def _qar_blocks(chunk, device):
+    """Concatenate questions (prompts.assemble_vcr_qar dicts + ``img_feats`` (Li, D)) into the Q->A block and the QA->R block of one batch, in
+    the reference's inputs-dict layout; img_feats is expanded per sequence on the device (vcr_collate_fn stacks it per sequence)."""
+    t = lambda x: torch.as_tensor(x)
+    blocks = []
+    for part in ("q_a", "qa_r"):
+        feats = []
+        for q in chunk:
+            f = t(q["img_feats"]).to(device, non_blocking=True)
+            n = q[part]["input_ids"].shape[0]
+            feats.append(f.unsqueeze(0).expand(n, -1, -1) if f.dim() == 2 else f)
+        blocks.append({"input_ids": torch.cat([t(q[part]["input_ids"]) for q in chunk], 0).to(device, non_blocking=True),
+                       "attention_mask": torch.cat([t(q[part]["input_mask"]) for q in chunk], 0).to(device, non_blocking=True),
+                       "token_type_ids": torch.cat([t(q[part]["segment_ids"]) for q in chunk], 0).to(device, non_blocking=True),
+                       "img_feats": torch.cat(feats, 0).float().contiguous()})
+    return blocks
+
+
+def _qar_layout(questions):
+    n_ans, n_rats = questions[0]["n_ans"], questions[0]["n_rats"]
+    if any(q["n_ans"] != n_ans or q["n_rats"] != n_rats for q in questions):
+        raise ValueError("VCR Q->AR: every question of a pass needs the same numbers of answers and rationales")
+    return n_ans, n_rats
+
+
+def val_vcr_qar(model, questions, device, batch_questions=4):
+    """Evaluation pass of vcr_qar_nsp_cpt.py:605-703 (evaluate) on VCRQAR_NSPCPT.  questions: prompts.assemble_vcr_qar dicts with ``img_feats``
+    (Li, D).  Questions are sharded over ranks (whole questions per rank); per batch ONE encoder pass runs over both blocks (qar_forward) and the
+    choice runs on the device (cpt_vcr_qar_choose); the fixed-shape (n_q, 2) predictions, (n_q, 3) flags and (n_q, n_ans + n_rats) choice scores
+    are gathered to every rank.  Accuracies follow the reference: results de-duplicated by questionId (last wins), divided by the number of
+    questions; "q_ar" is the reference's "Eval Accuracy".  Returns {"preds", "flags", "scores", "q_ids", "acc": {"q_a", "qa_r", "q_ar"}}."""
+    model.eval()
+    n_ans, n_rats = _qar_layout(questions)
+    rank, world = cdist.rank_world()
+    lo, hi = cdist.shard_range(len(questions), rank, world)
+    preds = torch.full((hi - lo, 2), -1, dtype=torch.int64, device=device)
+    flags = torch.zeros((hi - lo, 3), dtype=torch.uint8, device=device)
+    scores = torch.zeros((hi - lo, n_ans + n_rats), dtype=torch.float32, device=device)
+    for start in range(lo, hi, batch_questions):
+        chunk = questions[start:min(start + batch_questions, hi)]
+        qa, qr = _qar_blocks(chunk, device)
+        with torch.no_grad():
+            _, _, sc = model.qar_forward(qa, qr, return_scores=True)
+        nq = len(chunk)
+        B0 = nq * n_ans
+        p, f = scoring.vcr_qar_choose_device(sc[:B0], sc[B0:], [q["label"][0] for q in chunk], [q["label"][1] for q in chunk], n_ans, n_rats)
+        i = start - lo
+        preds[i:i + nq], flags[i:i + nq] = p, f
+        scores[i:i + nq, :n_ans] = sc[:B0].view(nq, n_ans)
+        scores[i:i + nq, n_ans:] = sc[B0:].view(nq, n_rats)
+    n = len(questions)
+    preds = cdist.gather_fixed(preds, n, fill=-1).cpu()
+    flags = cdist.gather_fixed(flags, n, fill=0).cpu()
+    scores = cdist.gather_fixed(scores, n, fill=0).cpu()
+    q_ids = [q["q_id"] for q in questions]
+    last = {}
+    for i, qid in enumerate(q_ids):        # de-duplication by questionId: the last entry wins (vcr_qar_nsp_cpt.py:682)
+        last[qid] = i
+    keep = sorted(last.values())
+    acc = {k: float(flags[keep, j].sum().item()) / n for j, k in enumerate(("q_a", "qa_r", "q_ar"))}
+    return {"preds": preds, "flags": flags, "scores": scores, "q_ids": q_ids, "acc": acc}
+
+
+def qar_accumulation(n_examples, per_gpu_train_batch_size, world_size, n_batches, num_train_epochs=1, max_steps=0):
+    """vcr_qar_nsp_cpt.py:399-407: gradient_accumulation_steps = max(1, len(dataset) // (per_gpu_bs * world)) -- one optimizer step per epoch --
+    and t_total (max_steps, else len(dataloader) // gradient_accumulation_steps * num_train_epochs).  Returns (gradient_accumulation_steps,
+    t_total)."""
+    gas = max(1, n_examples // (per_gpu_train_batch_size * world_size))
+    t_total = max_steps if max_steps > 0 else n_batches // gas * num_train_epochs
+    return gas, t_total
+
+
+def train_vcr_qar_batch(model, optimizer, scheduler, batches, opts, device, global_step=0):
+    """One epoch of vcr_qar_nsp_cpt.py:453-525 over ``batches`` (lists of prompts.assemble_vcr_qar dicts with img_feats, one list per micro-step):
+    class-0 labels of both blocks (qar_choice_labels), loss = q_a_loss + qa_r_loss from ONE encoder pass (qar_forward), divided by
+    opts.gradient_accumulation_steps when that is > 1, backward, torch.nn.utils.clip_grad_norm_(model.parameters(), opts.max_grad_norm) on EVERY
+    micro-step (in place on the accumulated gradient, as the reference), and every gradient_accumulation_steps micro-steps scheduler.step() BEFORE
+    optimizer.step(), then model.zero_grad().  Micro-steps that do not complete a window take no optimizer step and their gradient is kept (the
+    reference zeroes only after a step).  Returns (global_step, [loss tensors, as divided])."""
+    model.train()
+    gas = max(1, int(getattr(opts, "gradient_accumulation_steps", 1)))
+    max_norm = float(getattr(opts, "max_grad_norm", 1.0))
+    losses = []
+    for step, chunk in enumerate(batches):
+        n_ans, n_rats = _qar_layout(chunk)
+        qa, qr = _qar_blocks(chunk, device)
+        la, lr_ = scoring.qar_choice_labels([q["label"][0] for q in chunk], [q["label"][1] for q in chunk], n_ans, n_rats)
+        loss = model.qar_forward(qa, qr, la, lr_)[0]
+        if gas > 1:
+            loss = loss / gas
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)
+        losses.append(loss.detach())
+        if (step + 1) % gas == 0:
+            scheduler.step()
+            optimizer.step()
+            model.zero_grad()
+            global_step += 1
+    return global_step, losses

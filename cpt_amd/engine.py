@@ -25,7 +25,7 @@ def bucket_of(name, n_layers):
     LayerNorm and the region projection; 1 + l = encoder layer l; n_layers + 1 = pooler + task head."""
     if name.startswith("bert.encoder.layer."):
         return 1 + int(name.split(".")[3])
-    if name.startswith(("bert.pooler.", "cls.")):
+    if name.startswith(("bert.pooler.", "cls.", "cls_ans.", "cls_rat.")):
         return n_layers + 1
     return 0
 
@@ -373,7 +373,7 @@ class PackedModel(object):
                    layers=cfg.num_hidden_layers, vocab=cfg.vocab_size, img_dim=D, img_dim_pad=(D + 63) // 64 * 64,
                    max_pos=cfg.max_position_embeddings, type_vocab=cfg.type_vocab_size,
                    use_img_ln=1 if getattr(cfg, "use_img_layernorm", None) else 0,
-                   n_rel=getattr(cfg, "num_contrast_classes", 2) if self.head in ("pretrain", "nsp") else 0,
+                   n_rel=getattr(cfg, "num_contrast_classes", 2) if self.head in ("pretrain", "nsp", "qar") else 0,
                    dtype=L.CPT_BF16 if lp else (L.CPT_BF16X3_MASTERS if x3_train else (L.CPT_BF16X3 if x3 else L.CPT_F32)), ln_eps=cfg.layer_norm_eps,
                    img_ln_eps=getattr(cfg, "img_layer_norm_eps", cfg.layer_norm_eps))
         layers = (L.Layer * cfg.num_hidden_layers)()
@@ -410,6 +410,12 @@ class PackedModel(object):
         if self.head == "nsp":
             m.w_rel = mat("cls.weight")
             m.b_rel = vec("cls.bias")
+        elif self.head == "qar":
+            # head 0 (cls_ans) as the two-head kernel reads it (rel2_heads: fp32 in bf16x3 mode, not a split copy); head 1 travels in cpt_rel2.
+            # Only cpt_train_*_rel2 / cpt_rel2_scores read it: the qar forward asks cpt_model_fwd for CPT_OUT_POOLED only (forward() refuses
+            # OUT_REL for this head), never for the split-operand relation GEMM of CPT_OUT_REL.
+            m.w_rel = self.rel2_heads()[0]
+            m.b_rel = vec("cls_ans.bias")
         elif self.head != "none":
             hp = "cls." if self.head == "cpt" else "cls.predictions."
             m.w_tr = mat(hp + "transform.dense.weight")
@@ -425,6 +431,56 @@ class PackedModel(object):
             m.fold = C.cast(self._fold["arr"], C.POINTER(L.LayerFold))
         self._desc[key] = (m, layers)     # keep `layers` alive
         return self._desc[key]
+
+    def rel2_heads(self, train=False):
+        """(w0, b0, w1, b1) device pointers of VCR Q->AR's two relation heads (cls_ans, cls_rat) as cpt_rel2_scores / cpt_train_*_rel2 read
+        them: the bf16 shadow in bf16 mode, the fp32 master weights in every other mode (bf16x3 included: the head kernel is not a GEMM)."""
+        lp = self.dtype == "bf16"
+        base, esz = ((self.flat_lp, 2) if lp else (self.flat, 4))
+        w = lambda n: base.data_ptr() + self.offsets[n][0] * esz
+        v = lambda n: self.flat.data_ptr() + self.offsets[n][0] * 4
+        return w("cls_ans.weight"), v("cls_ans.bias"), w("cls_rat.weight"), v("cls_rat.bias")
+
+    def forward_rel2(self, input_ids, token_type_ids=None, attention_mask=None, position_ids=None, img_feats=None, B0=None, labels=None,
+                     labels_host=None):
+        """VCR Q->AR on one batch: rows [0, B0) through head 0 (cls_ans), rows [B0, B) through head 1 (cls_rat), one encoder pass
+        (cpt_model_fwd with CPT_OUT_POOLED), then the two heads in one launch (cpt_rel2_scores).  Returns {"rel": (B, n_rel), "score": (B,)
+        = 1 - softmax(rel)[:, 1], and with labels "loss": group-0 mean + group-1 mean (0-dim), "loss2": the two means}."""
+        if self.head != "qar":
+            raise RuntimeError("cpt_amd: forward_rel2 belongs to the VCR Q->AR model (head 'qar'), not '%s'" % self.head)
+        out = self.forward(input_ids, token_type_ids, attention_mask, position_ids, img_feats, flags=L.OUT_POOLED)
+        pooled = out["pooled"]
+        B = pooled.size(0)
+        B0 = B if B0 is None else int(B0)
+        n_rel = getattr(self.cfg, "num_contrast_classes", 2)
+        dev = pooled.device
+        rel = torch.empty((B, n_rel), device=dev, dtype=torch.float32)
+        score = torch.empty(B, device=dev, dtype=torch.float32) if n_rel >= 2 else None
+        w0, b0, w1, b1 = self.rel2_heads()
+        res = {"rel": rel, "score": score}
+        lab = dl = loss2 = None
+        ws, wsz = None, 0
+        if labels is not None:
+            lab = labels.to(device=dev, dtype=torch.int64).contiguous()
+            dl = torch.empty((B, n_rel), device=dev, dtype=torch.float32)
+            loss2 = torch.empty(3, device=dev, dtype=torch.float32)
+            need = L.lib().cpt_rel2_workspace_bytes(B)
+            ws = self._ws.get("rel2")
+            if ws is None or ws.numel() < need or ws.device != dev:
+                ws = torch.zeros(need, device=dev, dtype=torch.uint8)      # (the finish ticket must start at 0; every call leaves it 0)
+                self._ws["rel2"] = ws
+            wsz = ws.numel()
+            if labels_host is not None:
+                labels_host = labels_host.astype("int64", copy=False)
+        dtype = L.CPT_BF16 if self.dtype == "bf16" else L.CPT_F32
+        L.check(L.lib().cpt_rel2_scores(dtype, pooled.data_ptr(), B, self.cfg.hidden_size, n_rel, B0, w0, b0, w1, b1, L.ptr(lab),
+                                        labels_host.ctypes.data if labels_host is not None else None, rel.data_ptr(), L.ptr(score),
+                                        L.ptr(loss2), (loss2.data_ptr() + 8) if loss2 is not None else None, L.ptr(dl),
+                                        L.ptr(ws), wsz, L.stream_ptr()), "cpt_rel2_scores")
+        if loss2 is not None:
+            res["loss"] = loss2[2]
+            res["loss2"] = loss2[:2]
+        return res
 
     # ---- forward -------------------------------------------------------------------------
     def workspace(self, B, Lt, Li, flags):
@@ -443,6 +499,8 @@ class PackedModel(object):
         """Returns dict with the outputs selected by `flags` (see _lib.OUT_*).
         logit_cols (1-D int64 tensor of vocabulary ids, with OUT_MASK_LOGITS and no loss): ``logits`` holds those columns only, (B, len(logit_cols)),
         in list order -- the decoder then reads len(logit_cols) rows of its table instead of streaming it (cpt_outputs.logit_cols)."""
+        if self.head == "qar" and flags & L.OUT_REL:
+            raise RuntimeError("cpt_amd: the VCR Q->AR model has two relation heads: score them with forward_rel2 (cpt_rel2_scores), not OUT_REL")
         self.ensure_packed()
         self.refresh_shadow()
         if self.dtype == "bf16" and self.fold_ln:

@@ -297,6 +297,27 @@ def assemble_vcr(tokenizer, question, choices, colors, names, n_regions, label=N
             "mask_token_pos": mpos, "label": [0] if label is None else label, "q_id": int(q_id)}
 
 
+def assemble_vcr_qar(tokenizer, question, answers, rationales, colors, names, n_regions, label=None, q_id=0, max_seq_length=165,
+                     max_img_seq_length=45):
+    """VCRDataset.tensorize_example of the Q->AR driver (vcr_qar_nsp_cpt.py:164-198; VCR_QAR_Processor, utils/task_utils.py:421-470): two blocks.
+      "q_a":  one sequence per answer, exactly ``assemble_vcr`` (text_a = the question, text_b = the answer);
+      "qa_r": one sequence per rationale, text_a = the question's and the GROUND-TRUTH answer's token lists concatenated and written out
+              (_vcr_textize(question + answers[ans_label]), colourful), text_b = the rationale (colourful).
+    The QA->R block always takes the ground-truth answer, in evaluation too; ``label`` = (ans_label, rat_label) is therefore required: without
+    it the reference fails in _decode_label(None), here it raises ValueError.  Any number of rationales (the 4- and the 16-rationale layouts).
+    Each block is assemble_vcr's dict (its "label" is that block's label), plus "n_ans" / "n_rats" / "label" = (ans_label, rat_label)."""
+    if label is None:
+        raise ValueError("assemble_vcr_qar: the QA->R prompts need the ground-truth (answer, rationale) label (vcr_qar_nsp_cpt.py:180-186)")
+    ans_label, rat_label = int(label[0]), int(label[1])
+    if not 0 <= ans_label < len(answers):
+        raise ValueError("assemble_vcr_qar: answer label %d outside the %d answers" % (ans_label, len(answers)))
+    q_a = assemble_vcr(tokenizer, question, answers, colors, names, n_regions, label=ans_label, q_id=q_id, max_seq_length=max_seq_length,
+                       max_img_seq_length=max_img_seq_length)
+    qa_r = assemble_vcr(tokenizer, list(question) + list(answers[ans_label]), rationales, colors, names, n_regions, label=rat_label, q_id=q_id,
+                        max_seq_length=max_seq_length, max_img_seq_length=max_img_seq_length)
+    return {"q_a": q_a, "qa_r": qa_r, "n_ans": len(answers), "n_rats": len(rationales), "label": (ans_label, rat_label), "q_id": int(q_id)}
+
+
 # ---- VG-CPT predicate prompts -----------------------------------------------------------------------------------------------------
 # Counterparts of ZSLVGDataset.__getitem__ (/root/reference/Oscar/oscar/datasets/vg_test_dataset.py:37-77) and FtVGDataset.__getitem__
 # (datasets/vg_cpt_dataset.py:37-101) on one row parsed by cpt_amd.io.decode_row: info["objects"] = [objs, colors, names, rel_name] with

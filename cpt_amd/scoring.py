@@ -390,3 +390,67 @@ def eval_vg_reference(predictions, gts, modes=VG_MODES, n_slots=51):
     if set(VG_MODES) <= set(modes):
         out["string"] = format_vg_recall(out)
     return out
+
+
+# ---- VCR Q->AR (Oscar/oscar/fewshot/vcr_qar_nsp_cpt.py) ----------------------------------------------------------------------------------
+def qar_choice_labels(ans_labels, rat_labels, n_ans, n_rats, device=None):
+    """vcr_qar_nsp_cpt.py:462-472: class 0 at i * n_ans + ans_label of the Q->A block and at i * n_rats + rat_label of the QA->R block, 1 at every
+    other sequence.  Returns (q_a_cls_labels (n_q * n_ans,), qa_r_cls_labels (n_q * n_rats,)) int64."""
+    return nsp_choice_labels(ans_labels, n_ans, len(ans_labels) * n_ans, device), nsp_choice_labels(rat_labels, n_rats, len(rat_labels) * n_rats, device)
+
+
+def choice_scores(rel):
+    """evaluate()'s choice score (vcr_qar_nsp_cpt.py:641,650): 1 - softmax(rel)[:, 1]."""
+    return 1 - (rel[:, :].softmax(-1)[:, 1].view(-1))
+
+
+def vcr_qar_choose_reference(q_a_logits, qa_r_logits, ans_labels, rat_labels, n_ans, n_rats, q_ids=None):
+    """Host restatement of evaluate()'s per-question loop (vcr_qar_nsp_cpt.py:657-676) on the choice scores: the answer argmax, the rationale
+    argmax over all n_rats scores -- or, when n_rats > n_ans (16 rationales), over the slice [ans_label * n_ans, (ans_label + 1) * n_ans) of
+    them, block width n_ans as written, with the GROUND-TRUTH answer --, correct = both right.  Returns the result dicts the reference
+    pickles: questionId, answer [a, r], correct, gt [ans_label, rat_label], logits [q_a slice, qa_r slice]."""
+    out = []
+    n_q = len(ans_labels)
+    for n in range(n_q):
+        q_a_pred_logits = q_a_logits[n * n_ans:(n + 1) * n_ans]
+        q_a_pred = q_a_pred_logits.argmax()
+        ans_label = int(ans_labels[n])
+        if n_rats > n_ans:
+            qa_r_pred_logits = qa_r_logits[n * n_rats:(n + 1) * n_rats][ans_label * n_ans:(ans_label + 1) * n_ans]
+        else:
+            qa_r_pred_logits = qa_r_logits[n * n_rats:(n + 1) * n_rats]
+        qa_r_pred = qa_r_pred_logits.argmax()
+        rat_label = int(rat_labels[n])
+        out.append({"questionId": int(q_ids[n]) if q_ids is not None else n, "answer": [int(q_a_pred), int(qa_r_pred)],
+                    "correct": bool((ans_label == int(q_a_pred)) & (rat_label == int(qa_r_pred))), "gt": [ans_label, rat_label],
+                    "logits": [q_a_pred_logits.cpu().numpy(), qa_r_pred_logits.cpu().numpy()]})
+    return out
+
+
+def vcr_qar_choose_device(q_a_scores, qa_r_scores, ans_labels, rat_labels, n_ans, n_rats, counts=None):
+    """The same choice on the device, one launch (cpt_vcr_qar_choose): q_a_scores (n_q * n_ans,), qa_r_scores (n_q * n_rats,) fp32 device
+    tensors, labels (n_q,).  Returns (preds (n_q, 2) int64, flags (n_q, 3) uint8 = Q->A, QA->R, Q->AR correct); ``counts`` (3,) int32 device
+    tensor, optional: += the column sums of flags."""
+    from . import _lib as L
+    dev = q_a_scores.device
+    n_q = len(ans_labels)
+    qa = q_a_scores.contiguous().float()
+    qr = qa_r_scores.contiguous().float()
+    if qa.numel() != n_q * n_ans or qr.numel() != n_q * n_rats:
+        raise ValueError("vcr_qar_choose_device: %d / %d scores for %d questions of %d answers and %d rationales"
+                         % (qa.numel(), qr.numel(), n_q, n_ans, n_rats))
+    al = torch.as_tensor(ans_labels, dtype=torch.int64).to(dev).contiguous()
+    rl = torch.as_tensor(rat_labels, dtype=torch.int64).to(dev).contiguous()
+    preds = torch.empty((n_q, 2), dtype=torch.int64, device=dev)
+    flags = torch.empty((n_q, 3), dtype=torch.uint8, device=dev)
+    if counts is not None and (counts.dtype != torch.int32 or counts.numel() != 3 or not counts.is_contiguous()):
+        raise ValueError("vcr_qar_choose_device: counts must be a contiguous (3,) int32 tensor")
+    L.check(L.lib().cpt_vcr_qar_choose(qa.data_ptr(), qr.data_ptr(), n_q, n_ans, n_rats, al.data_ptr(), rl.data_ptr(), preds.data_ptr(),
+                                       flags.data_ptr(), L.ptr(counts), L.stream_ptr()), "cpt_vcr_qar_choose")
+    return preds, flags
+
+
+def vcr_qar_accuracy(results, n_examples):
+    """vcr_qar_nsp_cpt.py:682-685: results de-duplicated by questionId (a dict: the LAST entry wins), acc = correct / len(eval_dataset)."""
+    dic = {r["questionId"]: r for r in results}
+    return sum([x["correct"] for x in dic.values()]) / n_examples

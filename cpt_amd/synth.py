@@ -25,7 +25,8 @@ def param_specs(cfg, head="cpt"):
     Keys are the ones listed in SURVEY.md section 8(b) (verified there by
     instantiating the reference).  kind: 'w' Linear/Embedding weight, 'b' bias,
     'g' LayerNorm weight.  head: 'cpt' (REC_MLM_CPT, modeling_rec.py:100-109),
-    'pretrain' (BertImgForPreTraining, modeling_bert.py:981-991), 'nsp' (NSPCPT, modeling_vcr.py:79-92), 'none'.
+    'pretrain' (BertImgForPreTraining, modeling_bert.py:981-991), 'nsp' (NSPCPT, modeling_vcr.py:79-92),
+    'qar' (VCRQAR_NSPCPT, modeling_vcr.py:194-209), 'none'.
     """
     H, I, V = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size
     s = [("bert.embeddings.word_embeddings.weight", (V, H), "w"),
@@ -58,6 +59,9 @@ def param_specs(cfg, head="cpt"):
     if head == "nsp":          # NSPCPT after copy_from_pretraining_model: cls IS the seq_relationship Linear (modeling_vcr.py:90-92)
         n = getattr(cfg, "num_contrast_classes", 2)
         return s + [("cls.weight", (n, H), "w"), ("cls.bias", (n,), "b")]
+    if head == "qar":          # VCRQAR_NSPCPT after copy_from_pretraining_model: cls_ans / cls_rat are seq_relationship Linears (modeling_vcr.py:206-209)
+        n = getattr(cfg, "num_contrast_classes", 2)
+        return s + [("cls_ans.weight", (n, H), "w"), ("cls_ans.bias", (n,), "b"), ("cls_rat.weight", (n, H), "w"), ("cls_rat.bias", (n,), "b")]
     hp = "cls." if head == "cpt" else "cls.predictions."
     s += [(hp + "bias", (V,), "b"),
           (hp + "transform.dense.weight", (H, H), "w"), (hp + "transform.dense.bias", (H,), "b"),

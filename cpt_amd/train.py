@@ -24,9 +24,9 @@ NO_GRAD_PREFIXES = ("bert.pooler.", "cls.seq_relationship.")
 
 
 def no_grad_prefixes(head):
-    """Parameters outside the loss's graph: the MLM heads never touch the pooler / relation head; the NSP-CPT head
-    (NSPCPT, modeling_vcr.py:115-129) trains every parameter it holds."""
-    return () if head == "nsp" else NO_GRAD_PREFIXES
+    """Parameters outside the loss's graph: the MLM heads never touch the pooler / relation head; the NSP-CPT heads
+    (NSPCPT, modeling_vcr.py:115-129; VCRQAR_NSPCPT, :235-251) train every parameter they hold."""
+    return () if head in ("nsp", "qar") else NO_GRAD_PREFIXES
 
 
 def warmup_linear(step, warmup_step, tot_step):
@@ -98,11 +98,12 @@ class _TrainState(object):
                 g.img_ln_g = gp("bert.LayerNorm.weight")
                 g.img_ln_b = gp("bert.LayerNorm.bias")
             g.layers = C.cast(layers, C.POINTER(L.LayerGrads))
-            if eng.head == "nsp":
+            if eng.head in ("nsp", "qar"):
+                hw = "cls." if eng.head == "nsp" else "cls_ans."       # (VCR Q->AR: head 1's gradients travel in cpt_rel2, rel2_desc)
                 g.w_pool = gp("bert.pooler.dense.weight")
                 g.b_pool = gp("bert.pooler.dense.bias")
-                g.w_rel = gp("cls.weight")
-                g.b_rel = gp("cls.bias")
+                g.w_rel = gp(hw + "weight")
+                g.b_rel = gp(hw + "bias")
             else:
                 hp = "cls." if eng.head == "cpt" else "cls.predictions."
                 g.w_tr = gp(hp + "transform.dense.weight")
@@ -144,9 +145,20 @@ def _named_grad_views(eng, st):
     return out
 
 
+def rel2_desc(eng, st, B0, labels_host=None, score=None):
+    """cpt_rel2 of a VCR Q->AR training step: head 1 (cls_rat) as the step reads it, its gradient slots in the flat gradient buffer, B0."""
+    _, _, w1, b1 = eng.rel2_heads(train=True)
+    x = L.Rel2(B0=int(B0), w_rel1=w1, b_rel1=b1, score=L.ptr(score),
+               labels_host=labels_host.ctypes.data if labels_host is not None else None)
+    if st.grad is not None:
+        x.g_w_rel1 = st.grad.data_ptr() + eng.offsets["cls_rat.weight"][0] * 4
+        x.g_b_rel1 = st.grad.data_ptr() + eng.offsets["cls_rat.bias"][0] * 4
+    return x
+
+
 class _MLMLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, trigger, eng, tensors, drop):
+    def forward(ctx, trigger, eng, tensors, drop, rel2=None):
         ctx.eng = eng
         st = _state(eng)
         ids, seg, mask, pos, feats, mpos, labels, rseq = tensors
@@ -156,7 +168,7 @@ class _MLMLoss(torch.autograd.Function):
         m, _ = eng.descriptor(train=True)
         dev = eng.flat.device
         loss_acc = torch.empty(3, device=dev, dtype=torch.float32)      # {sum, count, mean}: the mean is written by the cross-entropy launch (cpt_outputs.loss_mean)
-        if eng.head == "nsp":       # relation scores of the pooled [CLS] instead of vocabulary logits of the [MASK] row
+        if eng.head in ("nsp", "qar"):       # relation scores of the pooled [CLS] instead of vocabulary logits of the [MASK] row
             logits = torch.empty((B, m.dims.n_rel), device=dev, dtype=torch.float32)
             o = L.Outputs(rel=logits.data_ptr(), loss=loss_acc.data_ptr(), loss_mean=loss_acc.data_ptr() + 8)
         else:
@@ -180,13 +192,21 @@ class _MLMLoss(torch.autograd.Function):
             except Exception as e:          # never let an exception cross the C frame
                 errs.append(e)
         cb = L.BUCKET_CB(before_bucket) if eng.pending is not None else L.NULL_CB
-        L.check(L.lib().cpt_train_fwd_ex(C.byref(m), C.byref(bt), C.byref(o), ws.data_ptr(), ws.numel(), L.stream_ptr(),
-                                         cb, None, C.byref(drop) if drop is not None else None), "cpt_train_fwd")
+        x = None
+        if rel2 is not None:        # VCR Q->AR: rows [0, B0) through cls_ans, [B0, B) through cls_rat, loss = the two group means summed
+            B0, labels_host = rel2
+            x = rel2_desc(eng, st, B0, labels_host)
+            L.check(L.lib().cpt_train_fwd_rel2(C.byref(m), C.byref(x), C.byref(bt), C.byref(o), ws.data_ptr(), ws.numel(), L.stream_ptr(),
+                                               cb, None, C.byref(drop) if drop is not None else None), "cpt_train_fwd_rel2")
+        else:
+            L.check(L.lib().cpt_train_fwd_ex(C.byref(m), C.byref(bt), C.byref(o), ws.data_ptr(), ws.numel(), L.stream_ptr(),
+                                             cb, None, C.byref(drop) if drop is not None else None), "cpt_train_fwd")
         if errs:
             raise errs[0]
         st.gen += 1
         ctx.gen = st.gen
         st.saved = (bt, tensors, st.gen, drop)    # keep the input tensors alive until backward; same masks in backward
+        st.saved_rel2 = (x, rel2)
         ctx.logits = logits
         ctx.mark_non_differentiable(logits)
         ctx.set_materialize_grads(False)      # (no zero-filled (R, V) gradient tensor for the scores on every backward)
@@ -212,8 +232,14 @@ class _MLMLoss(torch.autograd.Function):
         if accumulate:
             keep = st.grad.clone()
         g, _ = st.gdesc
+        x, _ = getattr(st, "saved_rel2", (None, None))
+        if x is not None:
+            x = rel2_desc(eng, st, x.B0)      # (the gradient buffer may have been made after the forward)
         # only what the backward ADDS into (bias / LayerNorm vectors, small tables) is cleared; weight gradients are written whole
-        L.check(L.lib().cpt_train_zero_grads(C.byref(m), C.byref(g), int(bt.Li), L.stream_ptr()), "cpt_train_zero_grads")
+        if x is not None:
+            L.check(L.lib().cpt_train_zero_grads_rel2(C.byref(m), C.byref(x), C.byref(g), int(bt.Li), L.stream_ptr()), "cpt_train_zero_grads_rel2")
+        else:
+            L.check(L.lib().cpt_train_zero_grads(C.byref(m), C.byref(g), int(bt.Li), L.stream_ptr()), "cpt_train_zero_grads")
         # the early reduce-scatter only when this backward completes the gradient: not while accumulating, not under no_sync()
         sync = st.sync if not (accumulate or st.defer) else None
         st.sent_version = None
@@ -226,8 +252,12 @@ class _MLMLoss(torch.autograd.Function):
                 errs.append(e)
         cb = L.BUCKET_CB(grads_ready) if sync is not None else L.NULL_CB     # (None: buckets are reduced in optimizer.step())
         gl = grad_loss.to(torch.float32).contiguous()          # device scalar: no host synchronisation between fwd and bwd
-        L.check(L.lib().cpt_train_bwd_ex(C.byref(m), C.byref(bt), C.byref(g), 1.0, gl.data_ptr(), st.ws.data_ptr(), st.ws.numel(),
-                                         L.stream_ptr(), cb, None, C.byref(drop) if drop is not None else None), "cpt_train_bwd")
+        if x is not None:
+            L.check(L.lib().cpt_train_bwd_rel2(C.byref(m), C.byref(x), C.byref(bt), C.byref(g), 1.0, gl.data_ptr(), st.ws.data_ptr(), st.ws.numel(),
+                                               L.stream_ptr(), cb, None, C.byref(drop) if drop is not None else None), "cpt_train_bwd_rel2")
+        else:
+            L.check(L.lib().cpt_train_bwd_ex(C.byref(m), C.byref(bt), C.byref(g), 1.0, gl.data_ptr(), st.ws.data_ptr(), st.ws.numel(),
+                                             L.stream_ptr(), cb, None, C.byref(drop) if drop is not None else None), "cpt_train_bwd")
         if errs:
             raise errs[0]
         if accumulate:
@@ -246,19 +276,24 @@ class _MLMLoss(torch.autograd.Function):
             # Views share their base's version counter, so step() can tell and refuse (FusedAdamW.step).
             st.sent_version = st.grad._version
         st.saved = None
-        return None, None, None, None
+        st.saved_rel2 = (None, None)
+        return None, None, None, None, None
 
 
-def mlm_loss_with_grad(model, input_ids, token_type_ids, attention_mask, labels, position_ids, img_feats, mask_token_pos, row_seq=None):
+def mlm_loss_with_grad(model, input_ids, token_type_ids, attention_mask, labels, position_ids, img_feats, mask_token_pos, row_seq=None,
+                       rel2=None):
     """(loss, prediction_scores) with autograd history, as REC_MLM_CPT.forward returns them
     (modeling_rec.py:147-152).  ``mask_token_pos`` is required: the loss only sees the [MASK] rows
     (fewshot/refcoco_cpt.py:231-233 puts -1 everywhere else).  For NSPCPT (head "nsp", modeling_vcr.py:115-129)
     ``labels`` are the (B,) next-sentence labels (-1 ignored), ``mask_token_pos`` is None and the second result is
-    the (B, num_contrast_classes) relation scores.
+    the (B, num_contrast_classes) relation scores.  ``rel2`` = (B0, host int64 labels or None): VCRQAR_NSPCPT (head "qar"), rows [0, B0)
+    through cls_ans and [B0, B) through cls_rat, the loss the sum of the two groups' means (cpt_train_fwd_rel2).
     ``row_seq`` (label grids with any number of labelled positions per sequence): ``labels`` / ``mask_token_pos`` then list the R
     labelled positions, ``row_seq`` (R,) the sequence each belongs to; the second result is the (R, V) scores of those rows."""
     eng = model._engine()
-    if mask_token_pos is None and eng.head != "nsp":
+    if (rel2 is not None) != (eng.head == "qar"):
+        raise RuntimeError("cpt_amd: the two-head step (rel2) belongs to the VCR Q->AR model and it alone")
+    if mask_token_pos is None and eng.head not in ("nsp", "qar"):
         raise NotImplementedError("cpt_amd: training needs mask_token_pos (the (B, L) label grid of the reference has "
                                   "exactly one labelled position per row: pass it as mask_token_pos)")
     if eng.dtype not in ("fp32", "bf16", "bf16x3"):
@@ -285,7 +320,10 @@ def mlm_loss_with_grad(model, input_ids, token_type_ids, attention_mask, labels,
     trigger = getattr(st, "trigger", None)      # one leaf per engine, made once: autograd needs an input that requires grad, backward returns None for it
     if trigger is None or trigger.device != eng.flat.device:
         trigger = st.trigger = torch.zeros((), device=eng.flat.device, requires_grad=True)
-    loss, logits = _MLMLoss.apply(trigger, eng, tensors, dropout_for(model, st))
+    if rel2 is not None:
+        loss, logits = _MLMLoss.apply(trigger, eng, tensors, dropout_for(model, st), rel2)
+    else:
+        loss, logits = _MLMLoss.apply(trigger, eng, tensors, dropout_for(model, st))
     return (loss, logits)
 
 

@@ -241,6 +241,44 @@ int cpt_vg_recall_ranks(const float* scores, int n_rows, int C, const int32_t* c
                         const int32_t* gt, int n_gt, int n_img, int32_t* out_rank, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * VCR Q->AR (Oscar/oscar/modeling/modeling_vcr.py:194-251 VCRQAR_NSPCPT, fewshot/vcr_qar_nsp_cpt.py): two relation heads on ONE batch.
+ * Added beside ABI 8, no struct changed.  Rows [0, B0) are the Q->A sequences and go through head 0 (cpt_model.w_rel / b_rel, cls_ans), rows
+ * [B0, B) are the QA->R sequences and go through head 1 (cpt_rel2.w_rel1 / b_rel1, cls_rat); the encoder and the pooler run once over all B
+ * rows.  B0 = B or B0 = 0 is a single-head batch (forward(head="ans" | "rat")).  Head weights: bf16 in CPT_BF16 mode (pooled is rounded to bf16
+ * where the head reads it), fp32 in every other mode (CPT_BF16X3 / CPT_BF16X3_MASTERS included); n_rel <= 64.
+ * Loss: CrossEntropyLoss(ignore_index=-1) per group, loss = mean over group 0 + mean over group 1 (the driver's q_a_loss + qa_r_loss); a group
+ * without rows adds nothing, a group whose rows are all ignored gives NaN.  Labels must lie in [-1, n_rel) (CPT_ERR_SHAPE otherwise): they are
+ * checked on the host from labels_host when given, else read back once (the call then waits for its stream).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t B0;                  /* rows of head 0: 0 <= B0 <= B */
+    const void* w_rel1;          /* head 1 [n_rel][H] (dtype as above) */
+    const float* b_rel1;         /* [n_rel] */
+    float* g_w_rel1;             /* cpt_train_bwd_rel2: head 1's weight gradient (WRITTEN, as g->w_rel) */
+    float* g_b_rel1;             /* cpt_train_bwd_rel2: head 1's bias gradient (ACCUMULATED, as g->b_rel; cpt_train_zero_grads_rel2 clears it) */
+    float* score;                /* optional [B] output: 1 - softmax(rel[s])[1], the choice score of evaluate() (vcr_qar_nsp_cpt.py:641,650) */
+    const int64_t* labels_host;  /* optional HOST copy of the [B] labels, for the range check without a stream wait */
+} cpt_rel2;
+
+/* Workspace of cpt_rel2_scores (bytes): B row losses + the finish ticket.  The ticket word must hold 0 before the first call (a zeroed
+ * workspace); every call leaves it 0. */
+size_t cpt_rel2_workspace_bytes(int B);
+/* The two heads on pooled rows [B][H] fp32 (cpt_model_fwd with CPT_OUT_POOLED), one launch: rel [B][n_rel]; score [B] (optional, n_rel >= 2);
+ * with labels [B] (device, optional): loss [2] = {group-0 mean, group-1 mean} and loss_mean [1] = their sum (either may be NULL), dlogits
+ * [B][n_rel] (optional) = d loss / d rel.  dtype: CPT_BF16 reads bf16 weights, anything else fp32 weights. */
+int cpt_rel2_scores(int dtype, const float* pooled, int B, int H, int n_rel, int B0, const void* w0, const float* b0, const void* w1, const float* b1,
+                    const int64_t* labels, const int64_t* labels_host, float* rel, float* score, float* loss, float* loss_mean, float* dlogits,
+                    void* workspace, size_t workspace_bytes, void* stream);
+/* Q->AR choice of evaluate() (vcr_qar_nsp_cpt.py:657-676) for n_q questions, one launch: q_a [n_q][n_ans] and qa_r [n_q][n_rats] choice scores
+ * (device fp32), ans_label / rat_label [n_q] (device int64).  Per question the answer argmax; the rationale argmax over all n_rats scores, or --
+ * n_rats > n_ans, the 16-rationale layout -- over the slice [ans_label * n_ans : (ans_label + 1) * n_ans] of them, as written, with Python's
+ * slice rules (negative bounds count from the end; an empty slice, where the reference's argmax would raise, gives -1).  torch.argmax rules: first maximum, NaN counts as the maximum.  preds [n_q][2] int64 = (answer,
+ * rationale); flags [n_q][3] uint8 = (ans_label == answer, rat_label == rationale, both); counts [3] int32 (optional) += the column sums of
+ * flags (device accumulation over evaluation batches). */
+int cpt_vcr_qar_choose(const float* q_a, const float* qa_r, int n_q, int n_ans, int n_rats, const int64_t* ans_label, const int64_t* rat_label,
+                       int64_t* preds, uint8_t* flags, int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Few-shot training step (Oscar/oscar/fewshot/refcoco_cpt.py:231-249): forward that keeps the
  * activations, backward into caller-owned fp32 gradient tensors laid out like the parameters,
  * fused AdamW.  [MASK]-rows mode only (the loss of modeling_rec.py:147-150 sees only those rows).
@@ -327,6 +365,17 @@ int cpt_train_fwd_ex(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
 int cpt_train_bwd_ex(const cpt_model* m, const cpt_batch* b, const cpt_model_grads* g, float loss_scale,
                      const float* loss_scale_dev, void* workspace, size_t workspace_bytes, void* stream,
                      cpt_bucket_fn grads_ready, void* user, const cpt_dropout* drop);
+/* VCR Q->AR (cpt_rel2 above): the training step of VCRQAR_NSPCPT: cpt_train_fwd_ex / cpt_train_bwd_ex / cpt_train_zero_grads with the NSP head (model without the MLM head,
+ * with w_pool and w_rel) and the second head in `x`; same workspace (cpt_train_workspace_bytes), dropout, bucket callbacks and write / accumulate
+ * contract.  The forward writes o->rel [B][n_rel], o->loss [2] = the two group means, o->loss_mean [1] = their sum (optional), x->score (optional).
+ * The backward is that of loss_scale (* *loss_scale_dev) times the summed loss; head 0's gradients go to g->w_rel / g->b_rel, head 1's to
+ * x->g_w_rel1 / x->g_b_rel1, the pooler's and the encoder's as in cpt_train_bwd. */
+int cpt_train_fwd_rel2(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, const cpt_outputs* o, void* workspace, size_t workspace_bytes,
+                       void* stream, cpt_bucket_fn before_bucket, void* user, const cpt_dropout* drop);
+int cpt_train_bwd_rel2(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, const cpt_model_grads* g, float loss_scale,
+                       const float* loss_scale_dev, void* workspace, size_t workspace_bytes, void* stream, cpt_bucket_fn grads_ready, void* user,
+                       const cpt_dropout* drop);
+int cpt_train_zero_grads_rel2(const cpt_model* m, const cpt_rel2* x, const cpt_model_grads* g, int Li, void* stream);
 
 /* torch.optim.AdamW update (fewshot/refcoco_cpt.py:343,249) over flat buffers of n fp32 elements
  * (n % 4 == 0).  code[i]: 0 = no gradient on this path (skipped), 1 = weight decay, 2 = no decay
