@@ -7,7 +7,9 @@ features of the RefCOCO shape, random-init weights (no checkpoint on the box).  
 REC_MLM_CPT forward over one batch already resident in HBM, producing the [MASK]-row logits
 (B x 30522 fp32) every reference consumer keeps (zeroshot/refcoco_cpt.py:219).
 
-    python bench.py [--gpus N --steps K --warmup W] [--batch 64] [--dtype bf16|fp32] [--all-rows]
+    python bench.py [--gpus N --steps K --warmup W] [--batch 64] [--dtype bf16|fp32] [--all-rows] [--full]
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line.  --full adds the legs behind
+the timed steps: sustained run, roofline / per-kernel figures, HBM kernels, other configurations, input pipeline, CPU baseline, parity.
 N > 1: one rank per GPU under torch.distributed.run (RCCL) -- the driver launches it that way, and a
 bare `python bench.py --gpus N` relaunches itself the same way (as a child process).  Inference shards sequences across
 ranks with no data-path collective (weak scaling: 64 sequences per GPU); --mode train runs the
@@ -567,7 +569,7 @@ def extra_configs(dev, model, cfg, seed):
     return out
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -578,6 +580,11 @@ def main():
     ap.add_argument("--mode", default="infer", choices=["infer", "train"],
                     help="infer: BASELINE configs[1] (default, the headline metric); train: few-shot step "
                          "(configs[2]: forward+backward+grad all-reduce+AdamW, 32 sequences per GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side legs: sustained run, train-mode comm block, roofline and per-kernel breakdown "
+                         "(with rocprofv3 --pmc child passes and the hipBLASLt yardstick), stand-alone HBM kernels, the other BASELINE configurations "
+                         "and input-pipeline legs, the CPU baseline and the parity check against the oracle (exit 3 on a bf16 parity failure).  "
+                         "Without it a run sets up, warms up, times the steps, dumps if asked and prints the line.  --no-* below drop single legs of --full")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed profiles/ summary instead of two rocprofv3 --pmc child passes of this run")
@@ -593,15 +600,22 @@ def main():
     ap.add_argument("--grad-wire", default="fp32", choices=["fp32", "bf16"], help="train mode: gradient dtype on the wire")
     ap.add_argument("--force-collectives", action="store_true",
                     help="debug, train mode at one rank: run the reduce-scatter / all-gather of the data-parallel step anyway (RCCL with one rank) so that the "
-                         "`comm` block of the line can be exercised on a 1-GPU box")
+                         "`comm` block of the line (--full) can be exercised on a 1-GPU box")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64, "
                          "at most 64 MB in all; larger arrays as a fixed seeded sample) -- the same arguments give the same inputs on every run "
                          "(training outputs then agree to rounding only: the backward adds some gradients with atomics)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run measures the headline figure only: every leg behind the timed steps is off (the train-mode comm block is gated on args.full)
+        args.no_cpu = args.no_roofline = args.no_live_pmc = args.no_io = args.no_extra = args.no_sustained = True
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: one rank per GPU under torch.distributed.run (the same command line the driver uses)
         import socket
@@ -747,7 +761,7 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = B * n_gpus * args.steps / dt
-    gpu_logits = out.detach().float().cpu() if (not train and args.workload == "refcoco" and not args.all_rows) else None
+    gpu_logits = out.detach().float().cpu() if (not args.no_cpu and not train and args.workload == "refcoco" and not args.all_rows) else None
 
     # sustained figure: the same step for >= 2 s of wall time (the K timed steps above last tens of milliseconds), same bracketing
     sustained = None
@@ -774,7 +788,7 @@ def main():
         sustained = {"pairs_per_s": round(B * n_gpus * n_sus / dts, 1), "steps": n_sus, "seconds": round(dts, 3), "ms_per_step": round(dts / n_sus * 1e3, 4)}
 
     comm = None
-    if train and getattr(opt, "sync", None) is not None and opt.sync.collectives and opt.sync.cuda:
+    if args.full and train and getattr(opt, "sync", None) is not None and opt.sync.collectives and opt.sync.cuda:
         # communication of the data-parallel step, measured over a few more steps with events on the communication stream (dist.ShardedGradSync.comm_report)
         opt.sync.profile = True
         opt.sync.comm_report(1)

@@ -2,7 +2,7 @@
 # same-box A/B of bench.py under different cpt_set_tuning settings: tools/ab_bench.sh "0=13" "0=3" ...
 for rep in 1 2; do
 for t in "$@"; do
-  python bench.py --no-cpu --no-io --steps 40 --tune "$t" 2>/dev/null | python -c "
+  python bench.py --full --no-cpu --no-io --steps 40 --tune "$t" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernel_ms_per_step']

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of developer builds of libcpt_hip.so on the bench workload (GPU box): tools/ab_libs.sh lib1.so lib2.so ...
 for l in "$@"; do
-  CPT_LIB_PATH=$l python bench.py --no-cpu --steps 30 --warmup 5 2>/dev/null | python -c "
+  CPT_LIB_PATH=$l python bench.py --full --no-cpu --steps 30 --warmup 5 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernel_ms_per_step']

@@ -3,7 +3,7 @@
 #  1 no operand DMA, 2 no fragment reads, 4 no MFMA, 8 no epilogue, 16 no epilogue math, 64 no epilogue stores,
 #  128 no residual loads, 256 no slab writes.   usage (GPU box): tools/abl_sweep.sh "0 8 16 64 ..."
 for a in $1; do
-  python bench.py --no-cpu --no-check --steps 30 --warmup 5 --tune "1=$a" 2>/dev/null | python -c "
+  python bench.py --full --no-cpu --no-check --steps 30 --warmup 5 --tune "1=$a" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernel_ms_per_step']

@@ -5,7 +5,7 @@
 R=$PWD; O=$R/gpurun_out/$1; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/inf_$C -- python $R/bench.py --steps 3 --warmup 1 --no-cpu --no-extra --no-sustained > $O/inf_$C.log 2>&1
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/inf_$C -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu --no-extra --no-sustained > $O/inf_$C.log 2>&1
   rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/trn_$C -- python $R/bench.py --steps 3 --warmup 1 --no-cpu --no-sustained --mode train > $O/trn_$C.log 2>&1
 done
 cd $R

@@ -5,10 +5,10 @@ T=$1; R=$PWD; O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 for w in gqa vcr; do
   rm -rf $O/${T}_prof_$w
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof_$w -- python $R/bench.py --steps 10 --warmup 3 --workload $w --no-cpu --no-roofline --no-extra > $O/${T}_bench_${w}_under_rocprof.json 2> $O/${T}_prof_$w.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof_$w -- python $R/bench.py --full --steps 10 --warmup 3 --workload $w --no-cpu --no-roofline --no-extra > $O/${T}_bench_${w}_under_rocprof.json 2> $O/${T}_prof_$w.log
 done
 rm -rf $O/${T}_prof_b4
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof_b4 -- python $R/bench.py --steps 10 --warmup 3 --mode train --batch 4 --no-cpu > $O/${T}_bench_train_b4_under_rocprof.json 2> $O/${T}_prof_b4.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof_b4 -- python $R/bench.py --full --steps 10 --warmup 3 --mode train --batch 4 --no-cpu > $O/${T}_bench_train_b4_under_rocprof.json 2> $O/${T}_prof_b4.log
 cd $R
 find $O/${T}_prof_gqa -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/${T}_bench_gqa_b256_bf16_kernel_stats.csv
 find $O/${T}_prof_vcr -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/${T}_bench_vcr_large_b32_bf16_kernel_stats.csv

@@ -1,7 +1,7 @@
 #!/bin/bash
 # start-skew sweep of the two-workgroups-per-CU GEMMs (cpt_set_tuning key 7); usage: tools/skew_sweep.sh "0 2052 ..."
 for a in $1; do
-  python bench.py --no-cpu --steps 30 --warmup 5 --tune "7=$a" 2>/dev/null | python -c "
+  python bench.py --full --no-cpu --steps 30 --warmup 5 --tune "7=$a" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernel_ms_per_step']

@@ -7,7 +7,7 @@ python bench.py --steps 20 --warmup 5 --mode train --batch 4 --no-cpu $TUNE > $O
 cd /tmp && export TMPDIR=/tmp
 for B in 32 4; do
   rm -rf $O/${T}_prof_train_b$B
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof_train_b$B -- python $R/bench.py --steps 10 --warmup 3 --mode train --batch $B --no-cpu $TUNE > /dev/null 2> $O/${T}_prof_train_b$B.log
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof_train_b$B -- python $R/bench.py --full --steps 10 --warmup 3 --mode train --batch $B --no-cpu $TUNE > /dev/null 2> $O/${T}_prof_train_b$B.log
   find $O/${T}_prof_train_b$B -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/${T}_train_b${B}_kernel_stats.csv
   rm -rf $O/${T}_prof_train_b$B
 done

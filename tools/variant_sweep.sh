@@ -1,7 +1,7 @@
 #!/bin/bash
 # per-kernel time of the bf16 bench under fixed GEMM tile shapes (cpt_set_tuning key 0); usage: tools/variant_sweep.sh "3 17 ..."
 for a in $1; do
-  python bench.py --no-cpu --no-check --steps 30 --warmup 5 --tune "0=$a" 2>/dev/null | python -c "
+  python bench.py --full --no-cpu --no-check --steps 30 --warmup 5 --tune "0=$a" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernel_ms_per_step']
