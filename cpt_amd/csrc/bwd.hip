@@ -775,8 +775,10 @@ __global__ __launch_bounds__(256) void scale_cast_kernel(const float* __restrict
     const float k = scale * (dscale ? dscale[0] : 1.f) / fmaxf(loss_acc ? loss_acc[1] : 1.f, 1.f);
     out[idx] = from_f32<TO>(c < C ? x[(size_t)r * C + c] * k : 0.f);
 }
-// ... with the column sums of the ROUNDED output added into colsum[c] (round 6: the decoder / relation bias gradient -- one launch instead of scale_cast +
-// colsum): one thread per column, the R <= 64 head rows in a loop, eight loads in flight
+// ... with the column sums added into colsum[c] (round 6: the decoder / relation bias gradient -- one launch instead of scale_cast + colsum): one thread
+// per column, 64 rows per workgroup row (grid.y) in a loop, eight loads in flight.  The sums are of the fp32 values, not of the bf16 copy the GEMMs
+// read: the bias is added wide in the forward, and summing the rounded copy put a systematic error of up to 2^-9 on the label columns (every row of
+// a label column holds the same (p - 1) / count, rounded the same way unless 1 / count is a bf16 number)
 template <typename TO>
 __global__ __launch_bounds__(256) void scale_cast_colsum_kernel(const float* __restrict__ x, const float* __restrict__ loss_acc, float scale,
                                                                 const float* __restrict__ dscale, TO* __restrict__ out, int R, int C, int ldo,
@@ -785,22 +787,21 @@ __global__ __launch_bounds__(256) void scale_cast_colsum_kernel(const float* __r
     // (One thread per column over all rows was 11.9 us at the 32 head rows of the 32-sequence step: four, then one long, batch of strided loads per thread.)
     __shared__ float part[4][64];
     const int cx = threadIdx.x & 63, rg = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cx;
+    const int c = blockIdx.x * 64 + cx, r0 = blockIdx.y * 64;
     const float k = scale * (dscale ? dscale[0] : 1.f) / fmaxf(loss_acc ? loss_acc[1] : 1.f, 1.f);
     float v[16];
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
-        const int r = rg + 4 * u;
+        const int r = r0 + rg + 4 * u;
         v[u] = (c < C && r < R) ? x[(size_t)r * C + c] * k : 0.f;
     }
     float acc = 0.f;
 #pragma unroll
     for (int u = 0; u < 16; ++u) {
-        const int r = rg + 4 * u;
+        const int r = r0 + rg + 4 * u;
         if (c < ldo && r < R) {
-            const TO o = from_f32<TO>(v[u]);
-            out[(size_t)r * ldo + c] = o;
-            acc += (float)o;
+            out[(size_t)r * ldo + c] = from_f32<TO>(v[u]);
+            acc += v[u];
         }
     }
     part[rg][cx] = acc;
@@ -809,8 +810,8 @@ __global__ __launch_bounds__(256) void scale_cast_colsum_kernel(const float* __r
 }
 int scale_cast(const float* x, const float* loss_acc, float scale, const float* dscale, void* out, int out_dtype, int R, int C, int ldo,
                hipStream_t s, float* colsum_out) {
-    if (colsum_out && R <= 64) {
-        dim3 grid((unsigned)((ldo + 63) / 64)), block(256);
+    if (colsum_out) {
+        dim3 grid((unsigned)((ldo + 63) / 64), (unsigned)((R + 63) / 64)), block(256);
         if (out_dtype == CPT_BF16) scale_cast_colsum_kernel<bf16><<<grid, block, 0, s>>>(x, loss_acc, scale, dscale, (bf16*)out, R, C, ldo, colsum_out);
         else scale_cast_colsum_kernel<float><<<grid, block, 0, s>>>(x, loss_acc, scale, dscale, (float*)out, R, C, ldo, colsum_out);
         return CPT_OK;
@@ -819,7 +820,6 @@ int scale_cast(const float* x, const float* loss_acc, float scale, const float* 
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
     if (out_dtype == CPT_BF16) scale_cast_kernel<bf16><<<grid, block, 0, s>>>(x, loss_acc, scale, dscale, (bf16*)out, R, C, ldo);
     else scale_cast_kernel<float><<<grid, block, 0, s>>>(x, loss_acc, scale, dscale, (float*)out, R, C, ldo);
-    if (colsum_out) return colsum(out, out_dtype, ldo, colsum_out, R, C, s);      // (many rows: the tiled column-sum launch)
     return CPT_OK;
 }
 

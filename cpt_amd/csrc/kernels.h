@@ -65,7 +65,7 @@ int gelu_bwd(const void* dh, const void* u, void* du, int dtype, size_t n, hipSt
 struct ColJob { const float* src; float *dst0, *dst1, *dst2; int rows, cols, row_stride, seg; };
 struct ColJobs { ColJob j[4]; int n; };
 int col_jobs_flush(const ColJobs& jobs, hipStream_t s);
-inline bool col_jobs_add(ColJobs& q, const float* src, int rows, int cols, int row_stride, int seg, float* d0, float* d1 = nullptr, float* d2 = nullptr) {
+[[nodiscard]] inline bool col_jobs_add(ColJobs& q, const float* src, int rows, int cols, int row_stride, int seg, float* d0, float* d1 = nullptr, float* d2 = nullptr) {
     if (q.n >= 4) return false;
     q.j[q.n++] = ColJob{src, d0, d1, d2, rows, cols, row_stride, seg};
     return true;

@@ -210,6 +210,17 @@ bool train_tail_on(const cpt_dims& d, const cpt_batch* b) {
            (long)b->B * 4 <= (long)b->B * (b->Lt + b->Li);
 }
 
+// queue a column-sum job behind the ones already waiting for a carrier launch; a full queue first goes out on a launch of its own, so no
+// partial sum is ever dropped
+int col_jobs_push(cpt::ColJobs& q, hipStream_t s, const float* src, int rows, int cols, int row_stride, int seg, float* d0, float* d1 = nullptr,
+                  float* d2 = nullptr) {
+    if (cpt::col_jobs_add(q, src, rows, cols, row_stride, seg, d0, d1, d2)) return CPT_OK;
+    const int rc = cpt::col_jobs_flush(q, s);
+    if (rc != CPT_OK) return rc;
+    q = cpt::ColJobs{};
+    return cpt::col_jobs_add(q, src, rows, cols, row_stride, seg, d0, d1, d2) ? CPT_OK : CPT_ERR_SHAPE;
+}
+
 }  // namespace
 
 // One Linear-shaped product out[Mr][N] = A[Mr][K] . W[N][K]^T of the training step.  fp32 / bf16: the library GEMM of that type.  bf16x3 (the parity mode at
@@ -710,7 +721,7 @@ static int train_bwd_impl(const cpt_model* m, const cpt_rel2* x, const cpt_batch
             TRY(cpt::ln_bwd(dxS > 1 ? (const float*)tA : dx, (const float*)LB(l, w.o_pre2), y.ln2_g, d.ln_eps, dpre, ph ? dmask_lp : dpre_lp, dt, gy.ln2_g, gy.ln2_b,
                             M, H, M, 0, 0, 0, s, part, w.lnp_bytes, ph ? &sp2 : nullptr, gy.b_out, &e), "ln_bwd(ffn)+dropout+bias");
             pend = cpt::ColJobs{};
-            cpt::col_jobs_add(pend, part, cpt::ln_bwd_part_rows(M), 3 * H, 3 * H, H, gy.ln2_g, gy.ln2_b, gy.b_out);
+            TRY(col_jobs_push(pend, s, part, cpt::ln_bwd_part_rows(M), 3 * H, 3 * H, H, gy.ln2_g, gy.ln2_b, gy.b_out), "column-sum jobs (ffn side)");
             lnp_turn ^= 1;
             if (l + 1 < d.layers) {      // the layer above is complete now: this launch added its attention-side LayerNorm's sums
                 if (qjob.S > 1) ready_after_triple = 1 + l + 1;      // (... but for its Q|K|V weight gradient, still in partial matrices)
@@ -738,7 +749,7 @@ static int train_bwd_impl(const cpt_model* m, const cpt_rel2* x, const cpt_batch
             TRY(cpt::colsum(dbig, dt, I, gy.b_in, M, I, s), "colsum(b_in)");
         } else if (rc) return rc;
         else if (!bin_parts) TRY(cpt::colsum(dbig, dt, I, gy.b_in, M, I, s), "colsum(b_in)");
-        else cpt::col_jobs_add(pend, (const float*)(ws + w.csp), (M + 31) / 32, I, I, I, gy.b_in);
+        else TRY(col_jobs_push(pend, s, (const float*)(ws + w.csp), (M + 31) / 32, I, I, I, gy.b_in), "column-sum jobs (b_in)");
         // round 3: where the three problems' tiles fit one round (hidden 768: 96 + 96 + 24), the two FFN weight gradients wait for the attention
         // output's and share ONE launch with it behind the attention-side LayerNorm backward (which then writes its low-precision output
         // to a second buffer: the FFN-side one is still an operand); Q|K|V runs alone behind the attention backward
@@ -767,7 +778,7 @@ static int train_bwd_impl(const cpt_model* m, const cpt_rel2* x, const cpt_batch
             TRY(cpt::ln_bwd(daS > 1 ? (const float*)tA : da, (const float*)LB(l, w.o_pre1), y.ln1_g, d.ln_eps, dpre, triple ? (void*)(ws + w.dlp2) : (ph ? dmask_lp : dpre_lp), dt, gy.ln1_g, gy.ln1_b,
                             M, H, M, 0, 0, 0, s, part, w.lnp_bytes, ph ? &sp1 : nullptr, gy.b_ao, &e), "ln_bwd(attn)+dropout+bias");
             pend = cpt::ColJobs{};
-            cpt::col_jobs_add(pend, part, cpt::ln_bwd_part_rows(M), 3 * H, 3 * H, H, gy.ln1_g, gy.ln1_b, gy.b_ao);
+            TRY(col_jobs_push(pend, s, part, cpt::ln_bwd_part_rows(M), 3 * H, 3 * H, H, gy.ln1_g, gy.ln1_b, gy.b_ao), "column-sum jobs (attention side)");
             lnp_turn ^= 1;
         } else {
         TRY(cpt::ln_bwd(da, (const float*)LB(l, w.o_pre1), y.ln1_g, d.ln_eps, dpre, dt == CPT_BF16 ? dpre_lp : nullptr, dt, gy.ln1_g, gy.ln1_b,

@@ -21,12 +21,54 @@ block cross-checked against the installed transformers==5.15 BERT modules.
 The fixtures live in ``tests/golden/`` and ``tests/test_oracle_golden.py`` checks
 this file against all of them.
 """
+import contextlib
 import math
 
 import torch
 import torch.nn.functional as F
 
 MASK_NEG = -10000.0
+
+# ---- bf16 design emulation (opt-in; off = the plain restatement above, bit for bit) ---------------------------------
+# The bf16 training step (DESIGN section 3, section 5.3) multiplies bf16 operands with fp32 accumulation: the weight shadow, the LayerNorm
+# outputs, Q / K / V, the attention probabilities, ctx and gelu(u) are stored as bf16 on the way forward, the incoming gradients of every
+# product as bf16 on the way back.  The residual stream, the LayerNorm statistics, softmax, GELU and the loss stay wide.  Under
+# ``emulate_bf16()`` every operand of a GEMM or attention matmul goes through ``_RoundBF16``: the design written as arithmetic, in whatever
+# dtype the caller runs (float64 as the yardstick).  Its distance from the plain run is the error the design is allowed to have.
+_EMU = [False]
+
+
+class _RoundBF16(torch.autograd.Function):
+    """Round to bf16 (nearest even) on the way forward, round the gradient to bf16 on the way back; the dtype is kept."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.to(torch.bfloat16).to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(torch.bfloat16).to(g.dtype)
+
+
+@contextlib.contextmanager
+def emulate_bf16(on=True):
+    """Run the oracle as the bf16 design (see above) inside the block."""
+    prev = _EMU[0]
+    _EMU[0] = bool(on)
+    try:
+        yield
+    finally:
+        _EMU[0] = prev
+
+
+def _lp(x):
+    """A product operand: rounded through bf16 under ``emulate_bf16()``, else ``x`` itself."""
+    return _RoundBF16.apply(x) if _EMU[0] else x
+
+
+def _linear(x, sd, key):
+    """nn.Linear ``key`` (``key``.weight, ``key``.bias) on x: one GEMM, both operands through ``_lp``, the bias added wide."""
+    return F.linear(_lp(x), _lp(sd[key + ".weight"]), sd[key + ".bias"])
 
 
 def gelu_erf(x):
@@ -58,7 +100,7 @@ def text_embeddings(sd, cfg, input_ids, token_type_ids, position_ids=None, prefi
     """BertEmbeddings.forward (third-party); call site modeling_bert.py:244-245."""
     B, Lt = input_ids.shape
     if position_ids is None:
-        position_ids = torch.arange(Lt, dtype=torch.long).unsqueeze(0).expand(B, Lt)
+        position_ids = torch.arange(Lt, dtype=torch.long, device=input_ids.device).unsqueeze(0).expand(B, Lt)
     if token_type_ids is None:
         token_type_ids = torch.zeros_like(input_ids)
     p = prefix + "embeddings."
@@ -70,7 +112,7 @@ def text_embeddings(sd, cfg, input_ids, token_type_ids, position_ids=None, prefi
 
 def image_embeddings(sd, cfg, img_feats, prefix="bert."):
     """modeling_bert.py:178,261-266 (dropout is identity in eval)."""
-    y = F.linear(img_feats, sd[prefix + "img_embedding.weight"], sd[prefix + "img_embedding.bias"])
+    y = _linear(img_feats, sd, prefix + "img_embedding")
     if cfg.get("use_img_layernorm"):
         y = layer_norm(y, sd[prefix + "LayerNorm.weight"], sd[prefix + "LayerNorm.bias"],
                        cfg["img_layer_norm_eps"])
@@ -82,7 +124,7 @@ def _drop(x, drop, key):
     to x.  drop None / key absent = eval mode (identity)."""
     if drop is None or key not in drop:
         return x
-    return x * drop[key].to(x.dtype).view(x.shape)
+    return x * drop[key].to(device=x.device, dtype=x.dtype).view(x.shape)
 
 
 def self_attention(sd, cfg, x, ext_mask, p, drop=None, layer=0):
@@ -90,16 +132,16 @@ def self_attention(sd, cfg, x, ext_mask, p, drop=None, layer=0):
     B, L, H = x.shape
     nh = cfg["num_attention_heads"]
     d = H // nh
-    q = F.linear(x, sd[p + "query.weight"], sd[p + "query.bias"])
-    k = F.linear(x, sd[p + "key.weight"], sd[p + "key.bias"])
-    v = F.linear(x, sd[p + "value.weight"], sd[p + "value.bias"])
+    q = _linear(x, sd, p + "query")
+    k = _linear(x, sd, p + "key")
+    v = _linear(x, sd, p + "value")
     q = q.view(B, L, nh, d).permute(0, 2, 1, 3)
     k = k.view(B, L, nh, d).permute(0, 2, 1, 3)
     v = v.view(B, L, nh, d).permute(0, 2, 1, 3)
-    s = torch.matmul(q, k.transpose(-1, -2)) / math.sqrt(d)
+    s = torch.matmul(_lp(q), _lp(k).transpose(-1, -2)) / math.sqrt(d)
     s = s + ext_mask
     pr = _drop(torch.softmax(s, dim=-1), drop, ("attn", layer))
-    ctx = torch.matmul(pr, v)
+    ctx = torch.matmul(_lp(pr), _lp(v))
     return ctx.permute(0, 2, 1, 3).contiguous().view(B, L, H)
 
 
@@ -109,11 +151,11 @@ def encoder_layer(sd, cfg, x, ext_mask, i, prefix="bert.", drop=None):
     p = "%sencoder.layer.%d." % (prefix, i)
     eps = cfg["layer_norm_eps"]
     ctx = self_attention(sd, cfg, x, ext_mask, p + "attention.self.", drop, i)
-    a = F.linear(ctx, sd[p + "attention.output.dense.weight"], sd[p + "attention.output.dense.bias"])
+    a = _linear(ctx, sd, p + "attention.output.dense")
     a = layer_norm(_drop(a, drop, ("ao", i)) + x, sd[p + "attention.output.LayerNorm.weight"],
                    sd[p + "attention.output.LayerNorm.bias"], eps)
-    h = gelu_erf(F.linear(a, sd[p + "intermediate.dense.weight"], sd[p + "intermediate.dense.bias"]))
-    o = F.linear(h, sd[p + "output.dense.weight"], sd[p + "output.dense.bias"])
+    h = gelu_erf(_linear(a, sd, p + "intermediate.dense"))
+    o = _linear(h, sd, p + "output.dense")
     return layer_norm(_drop(o, drop, ("out", i)) + a, sd[p + "output.LayerNorm.weight"], sd[p + "output.LayerNorm.bias"], eps)
 
 
@@ -141,10 +183,10 @@ def bert_img_forward(sd, cfg, input_ids, token_type_ids=None, attention_mask=Non
 def lm_head(sd, cfg, x, prefix="cls."):
     """BertLMPredictionHead (third-party) as wired by REC_MLM_CPT
     (modeling_rec.py:104-105,130-135,143): decoder weight tied to word embeddings."""
-    t = gelu_erf(F.linear(x, sd[prefix + "transform.dense.weight"], sd[prefix + "transform.dense.bias"]))
+    t = gelu_erf(_linear(x, sd, prefix + "transform.dense"))
     t = layer_norm(t, sd[prefix + "transform.LayerNorm.weight"], sd[prefix + "transform.LayerNorm.bias"],
                    cfg["layer_norm_eps"])
-    return F.linear(t, sd[prefix + "decoder.weight"]) + sd[prefix + "bias"]
+    return F.linear(_lp(t), _lp(sd[prefix + "decoder.weight"])) + sd[prefix + "bias"]
 
 
 def rec_mlm_cpt_forward(sd, cfg, input_ids, token_type_ids=None, attention_mask=None,
@@ -159,7 +201,7 @@ def rec_mlm_cpt_forward(sd, cfg, input_ids, token_type_ids=None, attention_mask=
     seq, _ = bert_img_forward(sd, cfg, input_ids, token_type_ids, attention_mask,
                               position_ids, img_feats, drop=drop)
     if mask_rows_only is not None:
-        rows = seq[torch.arange(seq.size(0)), mask_rows_only]
+        rows = seq[torch.arange(seq.size(0), device=seq.device), mask_rows_only]
         scores = lm_head(sd, cfg, rows)
     else:
         scores = lm_head(sd, cfg, seq)
@@ -167,7 +209,7 @@ def rec_mlm_cpt_forward(sd, cfg, input_ids, token_type_ids=None, attention_mask=
     if masked_lm_labels is not None:
         V = cfg["vocab_size"]
         if mask_rows_only is not None:
-            lab = masked_lm_labels[torch.arange(seq.size(0)), mask_rows_only]
+            lab = masked_lm_labels[torch.arange(seq.size(0), device=seq.device), mask_rows_only]
             loss = F.cross_entropy(scores.view(-1, V), lab.view(-1), ignore_index=-1)
         else:
             loss = F.cross_entropy(scores.view(-1, V), masked_lm_labels.view(-1), ignore_index=-1)
@@ -295,10 +337,14 @@ def warmup_linear_schedule(step, warmup_steps, t_total):
     return max(0.0, float(t_total - step) / float(max(1.0, t_total - warmup_steps)))
 
 
-def train_step_grads(sd, cfg, batch, names=None, drop=None):
+def train_step_grads(sd, cfg, batch, names=None, drop=None, labels=None, bf16=False, with_scores=False):
     """loss.backward() of fewshot/refcoco_cpt.py:231-248 with dropout disabled (or, with ``drop``, with the given masks):
     returns (loss, {name: grad}).  The tied decoder/word-embedding tensor gets the
-    sum of both contributions, exactly as autograd does for the shared Parameter."""
+    sum of both contributions, exactly as autograd does for the shared Parameter.
+
+    Runs on the device and in the dtype of ``sd`` / ``batch``.  ``labels``: a (B, L) label grid (-1 = no loss) instead of the
+    [MASK]-row labels; the head then runs on every row and the scores are those of the labelled rows in row-major order.
+    ``bf16``: run as the bf16 design (``emulate_bf16``).  ``with_scores``: also return the head rows' scores, (loss, grads, scores)."""
     tied = sd["cls.decoder.weight"].data_ptr() == sd["bert.embeddings.word_embeddings.weight"].data_ptr()
     leaves = {}
     for k, t in sd.items():
@@ -309,14 +355,22 @@ def train_step_grads(sd, cfg, batch, names=None, drop=None):
     if tied:
         work["cls.decoder.weight"] = leaves["bert.embeddings.word_embeddings.weight"]
     B = batch["input_ids"].size(0)
-    labels = torch.full(batch["attention_mask"].shape, -1, dtype=torch.long)
-    labels[torch.arange(B), batch["mask_token_pos"]] = batch["colors"]
-    loss, _ = rec_mlm_cpt_forward(work, cfg, batch["input_ids"], batch["segment_ids"],
-                                  batch["attention_mask"], masked_lm_labels=labels,
-                                  img_feats=batch["img_feats"],
-                                  mask_rows_only=batch["mask_token_pos"], drop=drop)
-    loss.backward()
+    dev = batch["input_ids"].device
+    rows = None
+    if labels is None:
+        labels = torch.full(batch["attention_mask"].shape, -1, dtype=torch.long, device=dev)
+        labels[torch.arange(B, device=dev), batch["mask_token_pos"]] = batch["colors"]
+        rows = batch["mask_token_pos"]
+    with emulate_bf16(bf16):
+        loss, scores = rec_mlm_cpt_forward(work, cfg, batch["input_ids"], batch["segment_ids"],
+                                           batch["attention_mask"], masked_lm_labels=labels,
+                                           img_feats=batch["img_feats"], mask_rows_only=rows, drop=drop)
+        loss.backward()
     grads = {k: (t.grad if t.grad is not None else None) for k, t in leaves.items()}
+    if with_scores:
+        if rows is None:
+            scores = scores[labels != -1]
+        return loss.detach(), grads, scores.detach()
     return loss.detach(), grads
 
 
