@@ -238,9 +238,6 @@ __global__ __launch_bounds__(ATT_THREADS, NKB >= 7 ? 2 : 1) void attention_kerne
         }
 }
 
-CPT_SWITCH(int g_attn_remap, 1);       // cpt_set_tuning(21, v): 0 = the (pair, tile) grid of rounds 1-2 (A/B)
-void set_attn_qt_all(int v) { CPT_SWITCH_SET(g_attn_remap = v); (void)v; }
-
 template <typename T, int NKB>
 static size_t att_lds_bytes() {
     constexpr int LP = NKB * 32;
@@ -258,7 +255,7 @@ static int att_launch(const void* qkv, const int64_t* mask, void* ctx, void* pro
         if (e != hipSuccess) return CPT_ERR_HIP - (int)e;
     }
     const int nqt = (L + 127) / 128;
-    const int remap = (nqt > 1 && g_attn_remap) ? 1 : 0;
+    const int remap = nqt > 1 ? 1 : 0;
     dim3 grid(remap ? ((B * heads + 7) / 8 * 8) * nqt : B * heads, remap ? 1 : nqt), block(ATT_THREADS);
     kern<<<grid, block, lds, s>>>((const T*)qkv, mask, (T*)ctx, (T*)probs, B, L, heads, dr, mask3, ctx_panel, remap, stats);
     return CPT_OK;

@@ -484,8 +484,6 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* __restr
     atomicAdd(c < H ? &dg[c] : (c < 2 * H ? &db[c - H] : &dbias[c - 2 * H]), a);
 }
 
-CPT_SWITCH(int g_lnb_rpb, 0);       // cpt_set_tuning(17, rows): rows per workgroup of the two-stage form (0: 8 from 2048 rows on, else 4 = one row per wave)
-void set_lnb_rpb(int v) { CPT_SWITCH_SET(g_lnb_rpb = v > 0 ? v : 0); (void)v; }
 
 // rows per workgroup / partial rows of the two-stage form for R rows (the training step sizes its partial buffers and chains its reductions with these)
 static int ln_bwd_rpb_two_stage(int R) { return g_lnb_rpb > 0 ? g_lnb_rpb : (R >= 2048 ? 8 : 4); }
@@ -1489,8 +1487,6 @@ __global__ __launch_bounds__(256, (TR && NKB <= 4) ? 2 : 1) void attn_bwd_mfma_k
     }
 }
 
-CPT_SWITCH(int g_attn_bwd_split, 1);       // cpt_set_tuning(38, v): two workgroups (one per phase) per (sequence, head) in small launches
-void set_attn_bwd_split(int v) { CPT_SWITCH_SET(g_attn_bwd_split = v); (void)v; }
 template <int NKB, bool TR = false>
 static int attn_bwd_mfma_launch(const void* qkv, const int64_t* mask, const void* dctx, void* dqkv, int B, int L, int heads, const DropSpec& dr,
                                 hipStream_t s, float* dbias, const void* ctx = nullptr, const float* stats = nullptr) {
@@ -1506,7 +1502,7 @@ static int attn_bwd_mfma_launch(const void* qkv, const int64_t* mask, const void
         done[have ? 1 : 0][dev] = true;
     }
     // two workgroups per (sequence, head), one per phase, where even those leave CUs idle (the phases run side by side instead of one after the other)
-    const int split = (have && NKB <= 4 && g_attn_bwd_split && 2 * B * heads <= 256) ? 1 : 0;
+    const int split = (have && NKB <= 4 && 2 * B * heads <= 256) ? 1 : 0;
     k<<<dim3(B * heads * (1 + split)), dim3(256), lds, s>>>((const bf16*)qkv, mask, (const bf16*)dctx, (bf16*)dqkv, B, L, heads, dr, dbias, (const bf16*)ctx, stats, split);
     return CPT_OK;
 }
@@ -2078,8 +2074,6 @@ int attention_bwd_x3(const float* qkv, const int64_t* attn_mask, const float* dc
     return attn_bwd_x3_long_launch<9>(qkv, attn_mask, dctx, dqkv, B, L, heads, dr, s, dbias);
 }
 
-CPT_SWITCH(int g_attn_bwd_variant, 1);      // 1: transpose-read MFMA kernels for bf16 (L <= 288); 0: generic kernel always; 2: L <= 128 through the older MFMA kernel with transposed tile copies
-void set_attn_bwd_variant(int v) { CPT_SWITCH_SET(g_attn_bwd_variant = v); (void)v; }
 
 static size_t attn_bwd_vg_lds(int L, int has_drop) { return ((size_t)L * 65 + 2 * 16 * 65 + (has_drop ? 3 : 2) * 16 * (L + 1) + L) * sizeof(float); }
 // Whether attention_bwd has a kernel for (dtype, L, dropout on the probabilities): asked by cpt_train_fwd so that an unsupported

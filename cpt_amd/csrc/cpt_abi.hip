@@ -8,7 +8,10 @@
 
 #include "kernels.h"
 
-namespace cpt { void set_ffn_2pass_min_tiles(int v); }
+// the switches are named without their namespace below, as the rest of this file's state is
+#define CPT_SWITCH_USING(key, name, dflt, lo, hi, desc) using cpt::name;
+CPT_SWITCH_TABLE(CPT_SWITCH_USING)
+#undef CPT_SWITCH_USING
 namespace {
 
 thread_local char g_err[512] = "";
@@ -124,14 +127,13 @@ FwdLayout fwd_layout(const cpt_dims& d, int B, int Lt, int Li, int flags) {
 
 }  // namespace
 
-// fused QKV projection + attention: form chosen by cpt_set_tuning(6, .)
-CPT_SWITCH(static int g_qkv_tiled, 1);    // form 3: read the K-tile-major weight copy (cpt_layer_fold.w_qkv_t) when the model carries one
+// fused QKV projection + attention: form chosen by cpt_set_tuning(6, .); form 3 reads the K-tile-major weight copy (cpt_layer_fold.w_qkv_t) when the model carries one
 static int qkv_attn(int config, const void* A, int lda, const void* W, int ldw, const float* bias, const float* st_in, const float* colc,
                     const float* cold, float eps, int hidden, const int64_t* mask, void* ctx, int ldo, int B, int L, int heads, int K,
                     hipStream_t s, const void* W_tiled, int ctx_panel = 0, int a_panel = 0) {
     if (config == 3) {
         if (cpt::qkv_attn3_eligible(L, heads, K)) {
-            const bool tl = W_tiled && g_qkv_tiled;
+            const bool tl = W_tiled != nullptr;
             return cpt::gemm_qkv_attn3(A, lda, tl ? W_tiled : W, ldw, bias, st_in, colc, cold, eps, hidden, mask, ctx, ldo, B, L, heads, K, s, tl ? 1 : 0, ctx_panel, a_panel);
         }
         config = 1;
@@ -139,6 +141,21 @@ static int qkv_attn(int config, const void* A, int lda, const void* W, int ldw, 
     if (ctx_panel || a_panel) return CPT_ERR_SHAPE;
     return cpt::gemm_qkv_attn(A, lda, W, ldw, bias, st_in, colc, cold, eps, hidden, mask, ctx, ldo, B, L, heads, K, config, s);
 }
+
+#ifdef CPT_ABLATION
+// development build: the one definition of every switch of the table (switches.h), and the table as data
+namespace cpt {
+#define CPT_SWITCH_DEF(key, name, dflt, lo, hi, desc) int name = dflt;
+CPT_SWITCH_TABLE(CPT_SWITCH_DEF)
+#undef CPT_SWITCH_DEF
+}  // namespace cpt
+namespace {
+struct SwitchRow { int key; int* var; int dflt, lo, hi; };
+#define CPT_SWITCH_ROW(key, name, dflt, lo, hi, desc) {key, &cpt::name, dflt, lo, hi},
+const SwitchRow g_switch_rows[] = { CPT_SWITCH_TABLE(CPT_SWITCH_ROW) };
+#undef CPT_SWITCH_ROW
+}  // namespace
+#endif
 
 extern "C" {
 
@@ -154,21 +171,6 @@ int cpt_check_device(int dev) {
     return CPT_OK;
 }
 
-CPT_SWITCH(static int g_fold_ln, 1);      // bf16 mode with cpt_model.fold: fold the encoder LayerNorms into the GEMMs (0 = run them as kernels)
-CPT_SWITCH(static int g_fuse_attn, 3);    // bf16, L <= 128: QKV projection + attention in one kernel (0 = two kernels; 1 = one workgroup per (sequence, head), two per CU; 2 = same, one per CU; 3 = one workgroup per (sequence, three heads) where heads % 3 == 0, else 1)
-CPT_SWITCH(static int g_lp_resid, 0);     // bf16 mode: keep the residual stream in bf16 only (A/B switch)
-CPT_SWITCH(static int g_panel, 1);        // fused bf16 encoder: ctx and the FFN activation travel in the fragment-major panel layout and the LayerNorm producers read them straight into registers (gemm_prod.hip) where the shapes allow
-CPT_SWITCH(static int g_x3_fuse, 1);      // bf16x3 parity mode: split copies written by the producing kernels (FFN-up GELU epilogue, LayerNorm passes) instead of stand-alone split3 passes (cpt_set_tuning key 23)
-CPT_SWITCH(static int g_rpanel, 1);       // round 5: the residual stream itself travels in the panel layout and the LayerNorm producers run their register-direct epilogue (gemm_prod.hip RP; cpt_set_tuning key 30)
-CPT_SWITCH(static int g_row_pad, 1);      // round 5: ragged batches run the full panel mode on rows padded up to its next shape (enc_rows; cpt_set_tuning key 32)
-CPT_SWITCH(static int g_tail, 1);         // round 5: with only [MASK] (or only [CLS]) rows read behind the encoder, the last layer's attention output / FFN / LayerNorms run on those rows alone (cpt_set_tuning key 31)
-CPT_SWITCH(static int g_prefetch, 1);     // panel mode: the 240-tile launches carry 16 workgroups that read the next launch's weights into the Infinity Cache (common.h prefetch_region)
-CPT_SWITCH(static int g_panel_ffn_multi, 1);   // panel layout for the FFN activation also when the producers run several rounds of tiles (cpt_set_tuning key 28; experiments)
-CPT_SWITCH(static int g_x3_attn, 1);      // bf16x3 parity mode: attention on bf16 MFMA with split operands (0: the fp32 MFMA kernel + a split3 pass over ctx)
-CPT_SWITCH(static int g_dec_pf_pct, 40);   // percent of the decoder table prefetched by the head's first launch (the rest: by its reduce + GELU + LayerNorm launch)
-CPT_SWITCH(static int g_embed_pad, 1);    // bf16 fused encoder: text embedding + region-feature pad/cast in one launch (cpt_set_tuning key 25)
-CPT_SWITCH(static int g_resid3, 1);       // fused bf16 encoder: residual stream in the 3-byte form (bf16 hi + int8 lo) instead of fp32 + bf16 copies
-
 int cpt_build_info(void) {
 #ifdef CPT_ABLATION
     return 1;
@@ -179,58 +181,25 @@ int cpt_build_info(void) {
 
 int cpt_set_tuning(int key, int value) {
 #ifndef CPT_ABLATION
-    // product build: every switch is a compile-time constant (common.h CPT_SWITCH) -- nothing to set, nothing global to restore
+    // product build: every switch is a compile-time constant (switches.h) -- nothing to set, nothing global to restore
     (void)value;
     if (key == -1) return CPT_OK;
     return fail(CPT_ERR_ARCH, "cpt_set_tuning(%d): the kernel-variant switches exist in the CPT_ABLATION build only (libcpt_hip_abl.so, CPT_AMD_ABLATION=1); "
                               "this library always runs its shipped configuration", key);
 #else
     if (key == -1) {       // every key back to its default (tests restore the library with this after every test)
-        g_lp_resid = 0; g_fold_ln = 1; g_fuse_attn = 3; g_resid3 = 1; g_embed_pad = 1; g_dec_pf_pct = 40; g_x3_attn = 1; g_panel_ffn_multi = 1; cpt::set_lncons4(1); g_qkv_tiled = 1; g_panel = 1; g_prefetch = 1; g_rpanel = 1; g_tail = 1; g_row_pad = 1;
-        cpt::set_gemm_variant(3); cpt::set_gemm_abl(0); cpt::set_q3_abl(0); cpt::set_attn_bwd_variant(1); cpt::set_splitk_target(384);
-        cpt::set_gemm_skew(0); cpt::set_wgrad_tn(1); cpt::set_ffn_dma_late(1); cpt::set_ffn_2pass_min_tiles(192); cpt::set_prod_abl(0); cpt::set_gemm_trace_filter(255, 0); cpt::set_lnb_rpb(0); cpt::set_bias_fuse(3); cpt::set_train_tail(1); cpt::set_nn_split2(1); cpt::set_nn_tile256(1); cpt::set_ln_lean(1); cpt::set_qkv_defer(1); cpt::set_narrow_tiles(1); cpt::set_attn_bwd_split(1); cpt::set_wgrad_pair(2); cpt::set_qkv_2pass(1); cpt::set_fwd_split2(1); g_x3_fuse = 1; cpt::set_attn_qt_all(1); cpt::set_prod_waves(0);
+        for (const SwitchRow& r : g_switch_rows) *r.var = r.dflt;
+        cpt::set_gemm_trace_filter(255, 0);
         return CPT_OK;
     }
-    if (key == 4) { g_lp_resid = value; return CPT_OK; }
-    if (key == 5) { g_fold_ln = value; return CPT_OK; }
-    if (key == 6) { g_fuse_attn = value; return CPT_OK; }
-    if (key == 0) { cpt::set_gemm_variant(value); return CPT_OK; }
-    if (key == 1) { cpt::set_gemm_abl(value); cpt::set_q3_abl(value); return CPT_OK; }
-    if (key == 2) { cpt::set_attn_bwd_variant(value); return CPT_OK; }
-    if (key == 3) { cpt::set_splitk_target(value); return CPT_OK; }
-    if (key == 7) { cpt::set_gemm_skew(value); return CPT_OK; }
-    if (key == 9) { g_resid3 = value; return CPT_OK; }
-    if (key == 11) { g_qkv_tiled = value; return CPT_OK; }
-    if (key == 12) { cpt::set_ffn_dma_late(value); return CPT_OK; }
-    if (key == 13) { cpt::set_prod_abl(value); return CPT_OK; }
-    if (key == 14) { g_panel = value; return CPT_OK; }
-    if (key == 16) { cpt::set_ffn_2pass_min_tiles(value); return CPT_OK; }
-    if (key == 15) { g_prefetch = value; return CPT_OK; }
-    if (key == 10) { cpt::set_wgrad_tn(value); return CPT_OK; }
-    if (key == 17) { cpt::set_lnb_rpb(value); return CPT_OK; }
-    if (key == 18) { cpt::set_bias_fuse(value); return CPT_OK; }
-    if (key == 19) { cpt::set_wgrad_pair(value); return CPT_OK; }
-    if (key == 20) { cpt::set_qkv_2pass(value); return CPT_OK; }
-    if (key == 21) { cpt::set_attn_qt_all(value); return CPT_OK; }
-    if (key == 22) { cpt::set_fwd_split2(value); return CPT_OK; }
-    if (key == 23) { g_x3_fuse = value; return CPT_OK; }
-    if (key == 24) { cpt::set_prod_waves(value); return CPT_OK; }
-    if (key == 25) { g_embed_pad = value; return CPT_OK; }
-    if (key == 27) { g_x3_attn = value; return CPT_OK; }
-    if (key == 28) { g_panel_ffn_multi = value; return CPT_OK; }
-    if (key == 30) { g_rpanel = value; return CPT_OK; }
-    if (key == 31) { g_tail = value; return CPT_OK; }
-    if (key == 32) { g_row_pad = value; return CPT_OK; }
-    if (key == 33) { cpt::set_train_tail(value); return CPT_OK; }
-    if (key == 34) { cpt::set_nn_split2(value); return CPT_OK; }
-    if (key == 35) { cpt::set_nn_tile256(value); return CPT_OK; }
-    if (key == 36) { cpt::set_ln_lean(value); return CPT_OK; }
-    if (key == 37) { cpt::set_qkv_defer(value); return CPT_OK; }
-    if (key == 38) { cpt::set_attn_bwd_split(value); return CPT_OK; }
-    if (key == 39) { cpt::set_narrow_tiles(value); return CPT_OK; }
-    if (key == 29) { cpt::set_lncons4(value); return CPT_OK; }
-    if (key == 26) { g_dec_pf_pct = value < 0 ? 0 : (value > 100 ? 100 : value); return CPT_OK; }
-    if (key == 8) { cpt::set_gemm_trace_filter(value & 255, value >> 8); return CPT_OK; }   // diagnostic builds: trace filter (epilogue id | K << 8); 255: all
+    if (key == 8) { cpt::set_gemm_trace_filter(value & 255, value >> 8); return CPT_OK; }   // a diagnostic, not a switch: trace filter (epilogue id | K << 8); 255: all
+    for (const SwitchRow& r : g_switch_rows) {
+        if (r.key != key) continue;
+        int v = value < r.lo ? r.lo : (value > r.hi ? r.hi : value);
+        if (key == 24 && v != 0 && v != 4) v = 8;      // three legal values inside the range: everything else is the 8-wave shape
+        *r.var = v;
+        return CPT_OK;
+    }
     return fail(CPT_ERR_SHAPE, "cpt_set_tuning: unknown key %d", key);
 #endif
 }
@@ -430,7 +399,7 @@ size_t cpt_fwd_workspace_bytes(const cpt_dims* d, int B, int Lt, int Li, int fla
 // 3-byte stream, (sequence, three heads) QKV + attention, two-pass FFN-up with panel output, both LayerNorm producers on the panel kernel.
 static bool rpanel_mode_rows(const cpt_dims& d, int L, int M, int flags, bool has_fold) {
     const int H = d.hidden, I = d.inter;
-    if (d.dtype != CPT_BF16 || !has_fold || !g_fold_ln || g_lp_resid || !g_resid3 || !g_panel || !g_rpanel) return false;
+    if (d.dtype != CPT_BF16 || !has_fold || !g_resid3 || !g_panel || !g_rpanel) return false;
     if (flags & CPT_ATTN_MASK_3D) return false;
     if (!(g_fuse_attn == 3 && L <= 128 && H % 64 == 0 && cpt::qkv_attn3_eligible(L, d.heads, H))) return false;
     if (!cpt::ffn_up_2pass_preferred(M, I, H) || !cpt::panel_eligible(M, H, H) || !cpt::panel_eligible(M, H, I)) return false;
@@ -447,7 +416,7 @@ namespace {
 int enc_rows(const cpt_dims& d, int B, int Lt, int Li, int flags) {
     const int L = Lt + Li;
     const long M = (long)B * L;
-    if (!g_row_pad || d.dtype != CPT_BF16 || rpanel_mode_rows(d, L, (int)M, flags, true)) return (int)M;
+    if (d.dtype != CPT_BF16 || rpanel_mode_rows(d, L, (int)M, flags, true)) return (int)M;
     for (long Mp = (M + 127) / 128 * 128; Mp <= M + M / 2; Mp += 128)
         if (rpanel_mode_rows(d, L, (int)Mp, flags, true)) {
             // ... unless the padded shape starts a nearly empty FURTHER round of tiles (70 x 120 rows -> 8448 rows = 264 producer tiles of 128 x 192 and 264 FFN-up
@@ -501,13 +470,13 @@ static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
     const int dt = x3 ? CPT_F32 : d.dtype;
     const bool lp = dt == CPT_BF16;
     void* splitbuf = ws + w.split;
-    // bf16x3, round 3: the FFN-up's GELU epilogue writes h as the split copy the FFN-down reads (key 23).  The fp32 FFN activation is then
+    // bf16x3, round 3: the FFN-up's GELU epilogue writes h as the split copy the FFN-down reads.  The fp32 FFN activation is then
     // never materialised, and its region [M][I] fp32 holds the FFN-up's own split input [M][3H] bf16 (asplit).  (The LayerNorm passes writing
     // the split inputs of QKV / FFN-up themselves was built too: the two stand-alone passes it saves cost what its strided 8-byte stores
     // add to the LayerNorm launches -- 5.78-5.94 vs 5.84 ms -- so they stay.)
     // round 4: the mode's attention on bf16 MFMA with split operands, writing ctx as the split copy the attention-output GEMM reads (key 27)
     const bool x3a = x3 && g_x3_attn && !(flags & CPT_ATTN_MASK_3D) && cpt::attention_x3_supported(L) && H % 8 == 0;
-    const bool x3f = x3 && g_x3_fuse && d.inter % 8 == 0 && (size_t)d.inter * 4 >= (size_t)3 * d.hidden * 2;
+    const bool x3f = x3 && d.inter % 8 == 0 && (size_t)d.inter * 4 >= (size_t)3 * d.hidden * 2;
     auto gm = [&](int epi, const void* A, int lda, const void* W, int K, const float* bias, const float* resid, int ldr, void* out,
                   int out_dt, int ldo, int Mr, int N) -> int {
         if (!x3) return cpt::gemm(dt, epi, A, lda, W, K, bias, resid, ldr, out, out_dt, ldo, Mr, N, K, s);
@@ -528,7 +497,7 @@ static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
     // 3-byte residual stream (common.h r3_encode): the pre-LayerNorm sums live as bf16 hi (x_lp / a_lp, the GEMM operands) +
     // int8 lo (the head of the x_f32 / a_f32 regions, which hold no fp32 tensor in this mode); the producers read and write
     // 3 + 3 bytes per element instead of 4 + 6, and the embedding kernels write their rows in that form directly.
-    const bool fold = lp && m->fold && g_fold_ln && !g_lp_resid;
+    const bool fold = lp && m->fold;
     const bool r3 = fold && g_resid3;
     void* x_lo = x_f32;
     void* a_lo = a_f32;
@@ -583,7 +552,7 @@ static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
     // there too (3.63 ms; cpt_set_tuning key 28 = 0 restores the row-major FFN activation for multi-round shapes)
     const bool panel_ffn = panel && ((long)(Me / 128) * (H / 192) <= 256 || g_panel_ffn_multi);
     if (rpanel && !panel_ffn) return fail(CPT_ERR_SHAPE, "cpt_model_fwd: internal: panel residual mode without the panel FFN activation");
-    const bool pfw = panel && g_prefetch;           // spare workgroups prefetch the next launch's weights (common.h prefetch_region)
+    const bool pfw = panel;           // spare workgroups prefetch the next launch's weights (common.h prefetch_region)
     // Round 5: the last layer on the head's rows only.  When nothing but the B [MASK] rows (MLM head) or nothing but the B [CLS] rows (pooler / relation
     // head) is read behind the encoder, the last layer's attention output, FFN and LayerNorms are row-wise work on rows nobody reads: they run on
     // those B rows (gather + previous LayerNorm, three K-split dense layers with their row passes) -- the reference computes every row and then indexes
@@ -603,7 +572,7 @@ static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
     // ... and for the fp32 mode: the same launches as its all-row form (cpt_gemm + layernorm_rows), on the B gathered rows
     const bool tail_f32 = g_tail && d.dtype == CPT_F32 && d.layers >= 2 && !(flags & (CPT_OUT_SEQ | CPT_OUT_ALL_LOGITS)) && want_mask != want_cls;
     const size_t dec_bytes_t = (size_t)d.vocab * H * 2;
-    const size_t dec_pf0_t = (want_mask && m->w_dec && g_prefetch && !cols) ? ((dec_bytes_t / 100 * (size_t)g_dec_pf_pct) & ~(size_t)1023) : 0;
+    const size_t dec_pf0_t = (want_mask && m->w_dec && !cols) ? ((dec_bytes_t / 100 * (size_t)g_dec_pf_pct) & ~(size_t)1023) : 0;
     if (Me != M && !rpanel) return fail(CPT_ERR_SHAPE, "cpt_model_fwd: internal: padded rows outside the panel residual mode");
     if (fold) {
         const int M = Me;       // (every launch of this block is row-wise or per sequence: the padded rows are computed and never read)
@@ -667,7 +636,7 @@ static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
                   size_t nqb = (size_t)3 * H * H * 2, nab = (size_t)H * H * 2;
                   if (pfw && l + 1 < d.layers) {
                       const cpt_layer_fold& fn = m->fold[l + 1];
-                      nq = (fn.w_qkv_t && g_qkv_tiled) ? fn.w_qkv_t : fn.w_qkv_f;
+                      nq = fn.w_qkv_t ? fn.w_qkv_t : fn.w_qkv_f;
                       na = m->layers[l + 1].w_ao;
                   } else if (pfw && (flags & CPT_OUT_MASK_LOGITS) && m->w_tr) {
                       // last layer: the MLM head's weights (transform dense, then the 47 MB tied decoder table streamed once by 64 rows)
@@ -704,7 +673,6 @@ static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
           if (x3a) TRY(cpt::attention_x3((const float*)qkv, b->attn_mask, nullptr, splitbuf, B, L, d.heads, s), "attention (split operands)");
           else TRY(cpt::attention(dt, qkv, b->attn_mask, ctx, nullptr, B, L, d.heads, s, nullptr, mask3), "attention"); }
         }
-        const bool lpr = lp && g_lp_resid;                       // residual operand read as bf16, fp32 copy not written
         const bool last = l + 1 == d.layers;
         if (tail_f32 && last) {
             Scope p(CPT_K_HEAD, s);
@@ -742,9 +710,9 @@ static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
         { Scope p(CPT_K_GEMM_AO, s);
           if (x3a) TRY(cpt::gemm(CPT_BF16, CPT_EPI_RESID, splitbuf, 3 * H, y.w_ao, 3 * H, y.b_ao, x_f32, H, pre, CPT_F32, H, M, H, 3 * H, s), "gemm(attn out, split ctx)");
           else
-          TRY(gm(lpr ? 5 : CPT_EPI_RESID, ctx, H, y.w_ao, H, y.b_ao, lpr ? (const float*)x_lp : x_f32, H, pre, CPT_F32, H, M, H), "gemm(attn out)"); }
+          TRY(gm(CPT_EPI_RESID, ctx, H, y.w_ao, H, y.b_ao, x_f32, H, pre, CPT_F32, H, M, H), "gemm(attn out)"); }
         { Scope p(CPT_K_LN, s);
-          TRY(cpt::layernorm_rows(pre, y.ln1_g, y.ln1_b, d.ln_eps, lpr ? nullptr : a_f32, lp ? a_lp : nullptr, dt, M, H, M, 0, 0, s), "layernorm(attn)"); }
+          TRY(cpt::layernorm_rows(pre, y.ln1_g, y.ln1_b, d.ln_eps, a_f32, lp ? a_lp : nullptr, dt, M, H, M, 0, 0, s), "layernorm(attn)"); }
         if (x3f) {
             // bf16x3 (round 3): the FFN-up's GELU epilogue writes h as the split copy the FFN-down reads; its own input split sits in the
             // (then unused) fp32 h region
@@ -757,10 +725,10 @@ static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
         { Scope p(CPT_K_GEMM_FFN1, s);
           TRY(gm(CPT_EPI_GELU, a_lp, H, y.w_in, H, y.b_in, nullptr, 0, ffn, dt, I, M, I), "gemm(ffn up)"); }
         { Scope p(CPT_K_GEMM_FFN2, s);
-          TRY(gm(lpr ? 5 : CPT_EPI_RESID, ffn, I, y.w_out, I, y.b_out, lpr ? (const float*)a_lp : a_f32, H, pre, CPT_F32, H, M, H), "gemm(ffn down)"); }
+          TRY(gm(CPT_EPI_RESID, ffn, I, y.w_out, I, y.b_out, a_f32, H, pre, CPT_F32, H, M, H), "gemm(ffn down)"); }
         }
         { Scope p(CPT_K_LN, s);
-          TRY(cpt::layernorm_rows(pre, y.ln2_g, y.ln2_b, d.ln_eps, (lpr && !(last && (flags & CPT_OUT_SEQ))) ? nullptr : x_f32, lp ? x_lp : nullptr, dt, M, H, M, 0, 0, s), "layernorm(ffn)"); }
+          TRY(cpt::layernorm_rows(pre, y.ln2_g, y.ln2_b, d.ln_eps, x_f32, lp ? x_lp : nullptr, dt, M, H, M, 0, 0, s), "layernorm(ffn)"); }
     }
 
     if ((flags & CPT_OUT_SEQ) && !seq_in_ws) {
@@ -817,7 +785,7 @@ static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
                 const cpt_layer& yl = m->layers[d.layers - 1];
                 float* rf = (float*)(ws + w.rows_f32);
                 if (r3) TRY(cpt::head_rows_ln3(x_lp, x_lo, b->mask_pos, yl.ln2_g, yl.ln2_b, d.ln_eps, g, B, L, H, s,
-                                               (g_prefetch && !cols) ? m->w_dec : nullptr, cols ? 0 : dec_pf0, rpanel), "gather + merge + layernorm([MASK] rows)");
+                                               !cols ? m->w_dec : nullptr, cols ? 0 : dec_pf0, rpanel), "gather + merge + layernorm([MASK] rows)");
                 else {
                 TRY(cpt::gather_rows(x_f32, CPT_F32, b->mask_pos, rf, B, L, H, s), "gather([MASK] pre-LN)");
                 TRY(cpt::layernorm_rows(rf, yl.ln2_g, yl.ln2_b, d.ln_eps, nullptr, g, dt, B, H, B, 0, 0, s), "layernorm([MASK] rows)");
@@ -829,7 +797,7 @@ static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
         }
         float* t1 = (float*)(ws + w.t1);
         void* t2 = ws + w.t2;
-        const bool dec_pf_split = g_prefetch && r3 && pre_ln && !all;
+        const bool dec_pf_split = r3 && pre_ln && !all;
         // bf16, [MASK] rows only: the transform GEMM splits K over workgroups (4 tiles of 12 K-tiles each would run on 4 CUs), the pass
         // behind it adds the partial matrices, applies GELU and the LayerNorm.  The split depends on H only: same bits for every batch.
         const int hs = cpt::head_transform_splits(H);

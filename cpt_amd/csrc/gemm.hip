@@ -1170,9 +1170,6 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_group3_kernel(TnProb p0, TnPro
 long long* g_gemm_trace = nullptr;
 int g_trace_epi = -1, g_trace_k = 0;       // diagnostic builds: stamp only launches of this epilogue / this K (-1 / 0: all)
 void set_gemm_trace_filter(int epi, int k) { g_trace_epi = epi == 255 ? -1 : epi; g_trace_k = k; }
-CPT_SWITCH(int g_gemm_abl, 0);
-CPT_SWITCH(int g_gemm_skew, 0);
-void set_gemm_skew(int v) { CPT_SWITCH_SET(g_gemm_skew = v); (void)v; }
 
 template <typename T, int EPI, typename OT, int TBM, int TBN, int WM, int WN, int STAGES, int EP = 1, int FD = 4, int OCC = 1, int TN = 0>
 static int launch_pipe(const T* A, int lda, const T* W, int ldw, const float* bias, const float* resid, int ldr,
@@ -1188,7 +1185,7 @@ static int launch_pipe(const T* A, int lda, const T* W, int ldw, const float* bi
     }
     EpiX e = {};
     if (ex) e = *ex;
-    e.skew = g_gemm_skew;
+    e.skew = 0;
     const int nwg = ((M + TBM - 1) / TBM) * ((N + TBN - 1) / TBN) * splitk;
     long long* tr = ((g_trace_epi < 0 || g_trace_epi == EPI) && (g_trace_k == 0 || g_trace_k == K)) ? g_gemm_trace : nullptr;
     kern<<<dim3(nwg), dim3(WM * WN * 64), LDS, s>>>(A, lda, W, ldw, bias, resid, ldr, out, ldo, M, N, K, splitk, tr, g_gemm_abl, e);
@@ -1196,7 +1193,6 @@ static int launch_pipe(const T* A, int lda, const T* W, int ldw, const float* bi
 }
 
 CallOverride& call_override() { static thread_local CallOverride o; return o; }
-CPT_SWITCH(int g_gemm_variant_sw, 3);
 #define g_gemm_variant (call_override().gemm_variant >= 0 ? call_override().gemm_variant : g_gemm_variant_sw)
 // g_gemm_variant: 0: generic register-staged kernel only; 3: pipelined kernel, tile shape chosen per GEMM; 10/11/13/14/15: one fixed shape
 
@@ -1211,10 +1207,8 @@ CPT_SWITCH(int g_gemm_variant_sw, 3);
 #define CPT_CFG_64x192 64, 192, 2, 2, 3                   // 4 waves of 32x96: twice the workgroups when M is small
 #define CPT_CFG_384x256 384, 256, 4, 2, 2, 1, 1, 1        // 8 waves of 96x128 (192 accumulator registers), the whole LDS as a 2-stage ring
 
-CPT_SWITCH(int g_narrow_tiles, 1);      // (values > 1, development build: the workgroup-count threshold itself instead of 128)
-#define NARROW_MAX (g_narrow_tiles > 1 ? (long)g_narrow_tiles : 128L)
-CPT_SWITCH(int g_narrow_dummy_, 0);      // cpt_set_tuning(39, v): 64 x 96 / 64 x 128 tiles for the FFN-up forward / GELU-gradient GEMMs where 64 x 192 tiles fill at most half the chip
-void set_narrow_tiles(int v) { CPT_SWITCH_SET(g_narrow_tiles = v); (void)v; }
+// 64 x 96 / 64 x 128 (and narrower) tiles for the GEMMs of a step at few rows: where 64 x 192 tiles would make at most this many workgroups (half the chip)
+constexpr long NARROW_MAX = 128;
 template <typename T, int EPI, typename OT>
 static void launch_fast(int variant, const T* A, int lda, const T* W, int ldw, const float* bias,
                         const float* resid, int ldr, OT* out, int ldo, int M, int N, int K, hipStream_t s,
@@ -1234,7 +1228,7 @@ static void launch_fast(int variant, const T* A, int lda, const T* W, int ldw, c
     // round 6, few rows (the training forward's FFN-up at 4 sequences per GPU: M = 480, N = 3072 is 128 tiles of 64 x 192): 64 x 96 tiles (2 waves of 32 x 96,
     // the same wave tile) put 256 workgroups on the chip with 20 instead of 32 KB of operands per K-tile
     if constexpr (EPI == CPT_EPI_GELU2 || (EPI == CPT_EPI_NONE && sizeof(T) == 2)) {      // (... and the plain epilogue: the forward Q|K|V at few rows, 96 tiles of 64 x 192)
-        if (variant == 3 && g_narrow_tiles && N % 96 == 0 && (long)((M + 63) / 64) * ((N + 191) / 192) <= NARROW_MAX) {
+        if (variant == 3 && N % 96 == 0 && (long)((M + 63) / 64) * ((N + 191) / 192) <= NARROW_MAX) {
             launch_pipe<T, EPI, OT, 64, 96, 2, 1, 3>(A, lda, W, ldw, bias, resid, ldr, out, ldo, M, N, K, s, 1, ex);
             return;
         }
@@ -1314,9 +1308,6 @@ static int launch_epi(int epi, const T* A, int lda, const T* W, int ldw, const f
             case CPT_EPI_RESID:
                 if (!resid) return CPT_ERR_SHAPE;
                 launch_fast<T, CPT_EPI_RESID, OT>(g_gemm_variant, A, lda, W, ldw, bias, resid, ldr, out, ldo, M, N, K, s); return CPT_OK;
-            case CPT_EPI_RESID_LP:
-                if (!resid || g_gemm_variant < 3) return CPT_ERR_SHAPE;
-                launch_fast<T, CPT_EPI_RESID_LP, OT>(g_gemm_variant, A, lda, W, ldw, bias, resid, ldr, out, ldo, M, N, K, s); return CPT_OK;
             default: return CPT_ERR_SHAPE;
         }
     }
@@ -1400,9 +1391,6 @@ int gemm_rows_split(const void* A, int lda, const void* W, int ldw, const float*
     return launch_pipe<bf16, CPT_EPI_NONE, float, 64, 192, 2, 2, 3>((const bf16*)A, lda, (const bf16*)W, ldw, bias, nullptr, 0, partials, N, M, N, K, s, rows_gemm_splits(K));
 }
 
-CPT_SWITCH(int g_splitk_target, 384);
-void set_splitk_target(int v) { CPT_SWITCH_SET(g_splitk_target = v); (void)v; }
-
 // out[M][N] (fp32, caller-zeroed or holding a partial sum) += A[M][K] . W[N][K]^T, K split over
 // enough workgroups to fill the chip; used for weight gradients (M, N small; K = rows of the batch)
 int gemm_splitk_accum(int dtype, const void* A, int lda, const void* W, int ldw, float* out, int ldo, int M, int N, int K, hipStream_t s) {
@@ -1473,7 +1461,7 @@ int gemm_tn(const void* A, int lda, const void* W, int ldw, float* out, int ldo,
     int rc;
     // (round 6: a short contraction that is not split and fills at most half the chip -- the Q|K|V weight gradient at 4 sequences per GPU, 72 tiles over
     // 8 K-tiles -- runs 64 x 192 tiles: 144 workgroups)
-    if (w192 && S == 1 && g_narrow_tiles && tiles <= NARROW_MAX)
+    if (w192 && S == 1 && tiles <= NARROW_MAX)
         rc = launch_pipe<bf16, CPT_EPI_NONE, float, 64, 192, 2, 2, 3, 1, 4, 1, 1>(a, lda, w, ldw, nullptr, nullptr, 0, dst, ldo, M, N, K, s, S, &ex);
     else
     if (w192) rc = launch_pipe<bf16, CPT_EPI_NONE, float, 128, 192, 4, 2, 3, 1, 4, 1, 1>(a, lda, w, ldw, nullptr, nullptr, 0, dst, ldo, M, N, K, s, S, &ex);
@@ -1522,7 +1510,7 @@ int gemm_tn_pair(const void* A0, int lda0, const void* W0, int ldw0, float* out0
     if ((t0 * S) % 8) return CPT_ERR_SHAPE;
     EpiX ex = {};
     ex.w_rows = k_rows;
-    ex.skew = g_gemm_skew;
+    ex.skew = 0;
     TnProb p0 = {(const bf16*)A0, (const bf16*)W0, out0, lda0, ldw0, N0, M0, N0, 0};
     TnProb p1 = {(const bf16*)A1, (const bf16*)W1, out1, lda1, ldw1, N1, M1, N1, 0};
     if (S > 1) {
@@ -1573,7 +1561,7 @@ int gemm_tn_triple(const void* A0, int lda0, const void* W0, int ldw0, float* ou
     const int t0 = (M0 / 128) * (N0 / 192), t1 = (M1 / 128) * (N1 / 192), t2 = (M2 / 128) * (N2 / 192);
     EpiX ex = {};
     ex.w_rows = k_rows;
-    ex.skew = g_gemm_skew;
+    ex.skew = 0;
     TnProb p0 = {(const bf16*)A0, (const bf16*)W0, out0, lda0, ldw0, N0, M0, N0, 0};
     TnProb p1 = {(const bf16*)A1, (const bf16*)W1, out1, lda1, ldw1, N1, M1, N1, 0};
     TnProb p2 = {(const bf16*)A2, (const bf16*)W2, out2, lda2, ldw2, N2, M2, N2, 0};
@@ -1657,17 +1645,13 @@ int gemm_nt_partials(const void* A, int lda, const void* W, int ldw, const float
     if (S < 3) return CPT_ERR_SHAPE;
     *S_out = S;
     // (round 6: where even the split leaves half the chip idle -- a short contraction, K = 768: 32 tiles x 4 splits -- 64 x 96 tiles, launch_fast's rule)
-    if (g_narrow_tiles && N % 96 == 0 && tiles * S <= NARROW_MAX)
+    if (N % 96 == 0 && tiles * S <= NARROW_MAX)
         return launch_pipe<bf16, CPT_EPI_NONE, float, 64, 96, 2, 1, 3>((const bf16*)A, lda, (const bf16*)W, ldw, bias, nullptr, 0, partials, N, M, N, K, s, S);
     return launch_pipe<bf16, CPT_EPI_NONE, float, 64, 192, 2, 2, 3>((const bf16*)A, lda, (const bf16*)W, ldw, bias, nullptr, 0, partials, N, M, N, K, s, S);
 }
 
 // ---- NN form: out[M][N] = A[M][K] . W[K][N] (+ resid), W = an nn.Linear weight [out_features = K][in_features = N] as stored:
 // the data gradients dX = dY . W of the backward pass without a transposed weight copy --------------------------------------
-CPT_SWITCH(int g_nn_tile256, 1);     // cpt_set_tuning(35, v): 1 (default) = the GELU-gradient data-gradient GEMM on 256 x 192 tiles where 128-row tiles would make 1..2 rounds
-void set_nn_tile256(int v) { CPT_SWITCH_SET(g_nn_tile256 = v); (void)v; }
-CPT_SWITCH(int g_nn_split2, 1);      // cpt_set_tuning(34, v): 1 (default) = the data-gradient GEMMs in front of a LayerNorm backward at 2048..6144 rows as two K-split bf16 partial matrices of 128 x 192 tiles
-void set_nn_split2(int v) { CPT_SWITCH_SET(g_nn_split2 = v); (void)v; }
 int gemm_nn_eligible(int M, int N, int K, int lda, int ldw) {
     return M > 0 && N > 0 && K > 0 && (N % 192 == 0 || N % 128 == 0) && K % 64 == 0 && lda % 8 == 0 && ldw % 8 == 0 && (size_t)K * ldw * 2 <= (size_t)0x7fffffff;
 }
@@ -1743,16 +1727,16 @@ int gemm_nn(const void* A, int lda, const void* W, int ldw, const float* resid, 
             // round 6: where 128-row tiles make between one and two rounds (M = 3840, N = 3072: 480 workgroups = 1.875 rounds on 256 CUs) and 256-row tiles make at
             // most one, take 256 x 192 (8 waves of 64 x 96, 2-stage ring of 112 KB): 240 workgroups, 1.71 instead of 2.4... MFMAs per KiB of operands UP (2.7)
             const long wg256 = (long)((M + 255) / 256) * (N / 192);
-            if (g_nn_tile256 && M >= 2048 && wg128 > 256 && wg128 < 512 && wg256 <= 256)
+            if (M >= 2048 && wg128 > 256 && wg128 < 512 && wg256 <= 256)
                 return launch_pipe<bf16, CPT_EPI_GELUGRAD, bf16, 256, 192, 4, 2, 2, 1, 4, 1, 2>(a, lda, w, ldw, nullptr, resid, ldr, (bf16*)out, ldo, M, N, K, s, 1, &ex);
             // round 6, few rows (4 sequences per GPU: M = 480, N = 3072 is 128 tiles of 64 x 192 -- half the chip idle, and the launch lasts as long as one
             // workgroup's twelve K-tiles): 64 x 128 tiles (4 waves of 32 x 64) put 192 workgroups on the chip with 24 instead of 32 KB of operands per K-tile
-            if (small && g_narrow_tiles && N % 128 == 0 && (long)((M + 63) / 64) * (N / 192) <= NARROW_MAX)
+            if (small && N % 128 == 0 && (long)((M + 63) / 64) * (N / 192) <= NARROW_MAX)
                 return launch_pipe<bf16, CPT_EPI_GELUGRAD, bf16, 64, 128, 2, 2, 3, 1, 4, 1, 2>(a, lda, w, ldw, nullptr, resid, ldr, (bf16*)out, ldo, M, N, K, s, 1, &ex);
             return small ? CPT_NN(CPT_EPI_GELUGRAD, bf16, 64, 2) : CPT_NN(CPT_EPI_GELUGRAD, bf16, 128, 4);
         }
         // (round 6: the attention output's data gradient at few rows is 32 tiles of 64 x 192: 64 x 64 tiles -- 2 waves of 32 x 64 -- make it 96 workgroups)
-        if (small && g_narrow_tiles && N % 64 == 0 && (long)((M + 63) / 64) * (N / 192) <= NARROW_MAX / 2)
+        if (small && N % 64 == 0 && (long)((M + 63) / 64) * (N / 192) <= NARROW_MAX / 2)
             return launch_pipe<bf16, CPT_EPI_NONE, bf16, 64, 64, 2, 1, 3, 1, 4, 1, 2>(a, lda, w, ldw, nullptr, resid, ldr, (bf16*)out, ldo, M, N, K, s, 1, &ex);
         return small ? CPT_NN(CPT_EPI_NONE, bf16, 64, 2) : CPT_NN(CPT_EPI_NONE, bf16, 128, 4);
     }
@@ -1818,9 +1802,6 @@ int gemm_gelu_x3(const void* A3, int lda, const void* W3, int ldw, const float* 
                                             (bf16*)out_split, 3 * N, M, N, K3, s, &ex);
     return CPT_OK;
 }
-
-CPT_SWITCH(int g_qkv_2pass, 1);
-void set_qkv_2pass(int v) { CPT_SWITCH_SET(g_qkv_2pass = v); (void)v; }
 
 int gemm_ln_cons(const void* A, int lda, const void* Wf, int ldw, const float* st_in, const float* colc, const float* cold,
                  float eps, int hidden, int gelu, void* out_lp, int ldo, int M, int N, int K, hipStream_t s, int out_panel, const void* pf, size_t pf_bytes, int a_panel) {
@@ -1891,7 +1872,7 @@ static int launch_qkv_attn(const bf16* A, int lda, const bf16* W, int ldw, const
         attr_done = true;
     }
     EpiX e = ex;
-    e.skew = g_gemm_skew;
+    e.skew = 0;
     long long* tr = (g_trace_epi < 0 || g_trace_epi == EPI) ? g_gemm_trace : nullptr;
     kern<<<dim3(B * ex.heads), dim3(512), LDS, s>>>(A, lda, W, ldw, bias, nullptr, 0, ctx, ldo, M, N, K, 1, tr, g_gemm_abl, e);
     return CPT_OK;
@@ -1916,8 +1897,6 @@ int gemm_qkv_attn(const void* A, int lda, const void* W, int ldw, const float* b
                  : launch_qkv_attn<CPT_EPI_ATTN, 2, 2, 2>(a, lda, w, ldw, bias, c, ldo, M, N, K, ex, B, s);
 }
 
-void set_gemm_variant(int v) { CPT_SWITCH_SET(g_gemm_variant_sw = v); (void)v; }
-void set_gemm_abl(int v) { CPT_SWITCH_SET(g_gemm_abl = v); (void)v; }
 void set_gemm_trace(void* p) { g_gemm_trace = (long long*)p; }
 
 }  // namespace cpt

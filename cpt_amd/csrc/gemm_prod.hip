@@ -672,10 +672,6 @@ __global__ __launch_bounds__(256) void panel_pack_kernel(const U* __restrict__ s
 
 extern long long* g_gemm_trace;
 extern int g_trace_k, g_trace_epi;       // diagnostics: stamp only launches of this K (0: all) / this epilogue id (-1: all; the producers are 11)
-CPT_SWITCH(int g_prod_abl, 0);          // timing experiments (cpt_set_tuning key 13), see prod3_panel_kernel
-void set_prod_abl(int v) { CPT_SWITCH_SET(g_prod_abl = v); (void)v; }
-CPT_SWITCH(int g_prod_waves, 0);        // wave shape of the tile (cpt_set_tuning key 24): 8 = 4 x 2 waves of 32 x 96, 4 = 4 x 1 waves of 32 x 192, 0 = by shape (4 when the tiles run several rounds); same bits
-void set_prod_waves(int v) { CPT_SWITCH_SET(g_prod_waves = (v == 4 || v == 0) ? v : 8); (void)v; }
 
 int panel_eligible(int M, int N, int K) { return M > 0 && M % TM == 0 && N > 0 && N % TN == 0 && K >= 512 && K % 256 == 0 && (size_t)M * K * 2 <= (size_t)0x7fffffff; }
 

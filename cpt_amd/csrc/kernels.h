@@ -231,7 +231,6 @@ int gemm_qkv_attn(const void* A, int lda, const void* W, int ldw, const float* b
 // round 3: the same fused launch with one workgroup per (sequence, three heads) (qkv_attn3.hip); needs qkv_attn3_eligible
 int qkv_attn3_eligible(int L, int heads, int K);
 void set_q3_trace(void* p);  // cpt_debug_gemm_trace: per-workgroup phase stamps of the kernel
-void set_q3_abl(int v);     // diagnostic builds (-DCPT_ABLATION): ablation bits of the kernel, see qkv_attn3.hip
 int gemm_qkv_attn3(const void* A, int lda, const void* W, int ldw, const float* bias, const float* st_in, const float* colc,
                    const float* cold, float eps, int hidden, const int64_t* mask, void* ctx, int ldo, int B, int L, int heads,
                    int K, hipStream_t s, int w_tiled = 0, int ctx_panel = 0, int a_panel = 0);     // a_panel (round 5): A = the residual stream's hi part in the panel layout     // w_tiled: W is the K-tile-major copy made by retile_k32; ctx_panel: ctx leaves in the panel layout (gemm_prod.hip), rows padded to a multiple of 32
@@ -242,27 +241,8 @@ int select_regions(const float* logits, int V, const int64_t* color_ids, int C, 
 int argmax_columns(const float* logits, int V, const int64_t* ids, int n_ids, int R, int64_t* out_idx, float* out_val, hipStream_t s);
 int fold_ln_weights(const float* W, const float* gamma, const float* beta, const float* bias, void* Wf_bf16, float* colc,
                     float* cold, int N, int K, hipStream_t s);
-void set_splitk_target(int v);
-void set_wgrad_pair(int v);  // training backward: the layer's weight gradients as two paired launches (1, default) or four single ones (0)
-void set_attn_qt_all(int v); // stand-alone attention, L > 128: the query tiles of a (sequence, head) as neighbouring workgroups of one XCD (1, default)
 // bf16x3 parity mode: FFN-up over the split operands (K3 = 3K) with the GELU epilogue writing h's [M][hi | hi | lo] split copy (ld 3N)
 int gemm_gelu_x3(const void* A3, int lda, const void* W3, int ldw, const float* bias, void* out_split, int M, int N, int K3, hipStream_t s);
-void set_fwd_split2(int v);  // training forward: FFN-down as two split-K partial matrices summed by the LayerNorm pass (1, default)
-void set_qkv_2pass(int v);   // stand-alone LayerNorm-consumer QKV projection through the GELU-less two-pass kernel (1, default)
-void set_nn_tile256(int v);
-void set_nn_split2(int v);   // training backward: data gradients in front of a LayerNorm backward as two K-split bf16 partial matrices (1, default)
-void set_ln_lean(int v);     // training forward: LayerNorm launches without fp32 output, residual re-formed by the next row pass (1, default)
-void set_attn_bwd_split(int v);   // attention backward: one workgroup per PHASE of a (sequence, head) pair where the launch fills less than half the chip (1, default)
-void set_narrow_tiles(int v);   // FFN-up forward / GELU-gradient GEMMs at few rows on 64 x 96 / 64 x 128 tiles (1, default)
-void set_qkv_defer(int v);   // training backward: Q|K|V weight-gradient partial sums inside the next layer's three-problem weight-gradient launch (1, default)
-void set_train_tail(int v);  // training step: the last encoder layer behind the attention on the head rows only (1, default)
-void set_bias_fuse(int v);   // training backward: bias-gradient column sums inside their producers (bit 0 b_in, bit 1 b_qkv)
-void set_lnb_rpb(int v);     // LayerNorm backward: rows per workgroup of the two-stage column-sum form (experiments)
-void set_wgrad_tn(int v);    // 1 (default): bf16 weight gradients through the TN GEMM; 0: explicit operand transposes
-void set_attn_bwd_variant(int v);
-void set_gemm_variant(int v);
-void set_gemm_abl(int v);
-void set_gemm_skew(int v);
 // FFN-up as one 384 x 256 two-pass kernel with its epilogue pipelined under the second pass (gemm_ffn.hip)
 int ffn_up_2pass_legal(int M, int N, int K);
 int ffn_up_2pass_preferred(int M, int N, int K);
@@ -273,10 +253,6 @@ int gemm_ffn_up_2pass(const void* A, int lda, const void* Wf, int ldw, const flo
 int gemm_lncons4(const void* A, int lda, const void* Wf, int ldw, const float* st_in, int st_parts, const float* colc, const float* cold,
                  float eps, int hidden, void* out, int ldo, int M, int N, int K, hipStream_t s, int out_panel, const void* pf, size_t pf_bytes, int gelu);
 int lncons4_enabled();
-void set_lncons4(int v);
-void set_ffn_dma_late(int v);
-void set_prod_abl(int v);    // timing experiments of the panel producer (gemm_prod.hip)
-void set_prod_waves(int v);  // wave shape of the panel producer: 8 (4 x 2 waves of 32 x 96) or 4 (4 x 1 waves of 32 x 192)
 // Per-CALL kernel choice for the operator-level test entry points (cpt_gemm_tile, cpt_gemm_ln_cons_tile, cpt_gemm_ln_prod3_panel_waves, the
 // waves argument of cpt_gemm_ln_prod3_rpanel): thread-local, set for the duration of one entry-point call by an OverrideScope and restored on
 // return -- no process-global state, other threads and later calls are untouched.  -1 = the library's own choice.

@@ -366,7 +366,6 @@ int q3_launch(const Q3Args& a, int B, hipStream_t s) {
 
 }  // namespace
 
-CPT_SWITCH(int g_q3_abl, 0);
 extern int g_trace_epi;
 long long* g_q3_trace = nullptr;
 void set_q3_trace(void* p) { g_q3_trace = (long long*)p; }
@@ -389,8 +388,8 @@ int gemm_qkv_attn3(const void* A, int lda, const void* W, int ldw, const float* 
     a.trace = (g_trace_epi < 0 || g_trace_epi == 10) ? g_q3_trace : nullptr;      // (diagnostics: trace filter by epilogue id, 10 = fused QKV + attention)
     a.mask = mask; a.ctx = (bf16*)ctx; a.ldo = ldo; a.M = B * L; a.K = K; a.L = L; a.heads = heads;
 #ifdef CPT_ABLATION      // diagnostic builds only (tools/abl_sweep.sh, cpt_set_tuning(1, bits)): timing instantiations with GARBAGE results; row-major ctx only
-    if (st_in && g_q3_abl && ctx_panel) return CPT_ERR_SHAPE;
-    if (st_in) switch (g_q3_abl) {
+    if (st_in && g_gemm_abl && ctx_panel) return CPT_ERR_SHAPE;
+    if (st_in) switch (g_gemm_abl) {
         case 1: return q3_launch<true, 1>(a, B, s);
         case 2: return q3_launch<true, 2>(a, B, s);
         case 3: return q3_launch<true, 3>(a, B, s);
@@ -405,6 +404,5 @@ int gemm_qkv_attn3(const void* A, int lda, const void* W, int ldw, const float* 
     if (ctx_panel) return st_in ? q3_launch<true, 0, true>(a, B, s) : q3_launch<false, 0, true>(a, B, s);
     return st_in ? q3_launch<true>(a, B, s) : q3_launch<false>(a, B, s);
 }
-void set_q3_abl(int v) { CPT_SWITCH_SET(g_q3_abl = v); (void)v; }
 
 }  // namespace cpt

@@ -11,35 +11,8 @@
 namespace cpt { int abi_fail(int code, const char* fmt, ...); int abi_check(int rc, const char* what); }
 using cpt::abi_check;
 using cpt::abi_fail;
-
-namespace cpt { CPT_SWITCH(int g_wgrad_tn, 1); void set_wgrad_tn(int v) { CPT_SWITCH_SET(g_wgrad_tn = v); (void)v; } }
-using cpt::g_wgrad_tn;
-// cpt_set_tuning(18, bits): bias-gradient column sums inside their producers -- bit 0: b_in in the GELU-gradient epilogue of
-// dgrad(ffn down) (round 6: as partial rows added up by a later launch's column-sum job; round 3's end-of-launch atomics cost more than the colsum launch, gemm.hip), bit 1: b_qkv in the attention
-// backward kernel (on: 43.3 vs 42.0 us per launch, no colsum launch); a cleared bit runs the stand-alone colsum launch instead
-// cpt_set_tuning(19, v): 2 (default) = FFN down | FFN up | attention output in ONE launch (216 workgroups, whole contraction each) + Q|K|V alone
-// with its own three-way split, where the shapes allow it (else as 1); 1 = two paired launches (gemm_tn_pair); 0 = four single ones
-namespace cpt { CPT_SWITCH(int g_wgrad_pair, 2); void set_wgrad_pair(int v) { CPT_SWITCH_SET(g_wgrad_pair = v); (void)v; } }
-using cpt::g_wgrad_pair;
-// cpt_set_tuning(22, v): 1 (default) = the FFN-down of the training forward runs on 128 x 192 tiles with K split in two (gemm_img_proj's
-// kernel) and the dropout + residual + LayerNorm pass adds the two partial matrices, 0 = 64 x 192 tiles over the whole K
-namespace cpt { CPT_SWITCH(int g_fwd_split2, 1); void set_fwd_split2(int v) { CPT_SWITCH_SET(g_fwd_split2 = v); (void)v; } }
-using cpt::g_fwd_split2;
-// cpt_set_tuning(33, v): 1 (default) = the LAST encoder layer's attention output, FFN and both LayerNorms run on the head's rows only (one per
-// sequence: the [MASK] row, or [CLS] for the NSP head) in the training forward AND backward -- every other row of that layer's output is dead
-// (the loss reads B rows; modeling_rec.py:142-150) and so is its gradient; 0 = all rows
-// cpt_set_tuning(36, v): 1 (default) = with hidden dropout the LayerNorm launches of the training forward write no fp32 output; the row pass behind
-// re-forms the residual from the pre-LayerNorm rows kept for the backward, 0 = fp32 outputs written and read back
-namespace cpt { CPT_SWITCH(int g_ln_lean, 1); void set_ln_lean(int v) { CPT_SWITCH_SET(g_ln_lean = v); (void)v; } }
-using cpt::g_ln_lean;
-// cpt_set_tuning(37, v): 1 (default) = the K-split partial matrices of a layer's Q|K|V weight gradient are added up by the spare workgroups of the NEXT layer's
-// three-problem weight-gradient launch (no reduction launch), 0 = reduction launch behind the split launch
-namespace cpt { CPT_SWITCH(int g_qkv_defer, 1); void set_qkv_defer(int v) { CPT_SWITCH_SET(g_qkv_defer = v); (void)v; } }
-using cpt::g_qkv_defer;
-namespace cpt { CPT_SWITCH(int g_train_tail, 1); void set_train_tail(int v) { CPT_SWITCH_SET(g_train_tail = v); (void)v; } }
-using cpt::g_train_tail;
-namespace cpt { CPT_SWITCH(int g_bias_fuse, 3); void set_bias_fuse(int v) { CPT_SWITCH_SET(g_bias_fuse = v); (void)v; } }
-using cpt::g_bias_fuse;
+// the switches of this file (switches.h has the table) are named without their namespace below
+using cpt::g_wgrad_tn; using cpt::g_bias_fuse; using cpt::g_wgrad_pair; using cpt::g_fwd_split2; using cpt::g_ln_lean; using cpt::g_qkv_defer;
 
 namespace {
 
@@ -204,10 +177,14 @@ int check_rel2(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, const 
     return cpt::rel2_check_labels(b->labels, x->labels_host, b->B, n_rel, who, (hipStream_t)stream);
 }
 
-// the pruned last layer (g_train_tail): bf16 step, one head row per sequence (no label grid), tile-aligned hidden sizes, 2-D mask
+// The pruned last layer: the LAST encoder layer's attention output, FFN and both LayerNorms run on the head's rows only (one per sequence: the
+// [MASK] row, or [CLS] for the NSP head) in the training forward AND backward -- every other row of that layer's output is dead (the loss reads
+// B rows; modeling_rec.py:142-150) and so is its gradient.  bf16 step, no label grid, tile-aligned hidden sizes, 2-D mask.  cpt_train_fwd and
+// cpt_train_bwd both ask exactly this predicate of (dims, batch): the backward reads the buffers the forward wrote under the same answer, which
+// is why a switch (g_wgrad_tn) must not change between the two calls (include/cpt_hip_debug.h).
 bool train_tail_on(const cpt_dims& d, const cpt_batch* b) {
-    return g_train_tail && g_wgrad_tn && d.dtype == CPT_BF16 && b->n_rows == 0 && d.layers >= 1 && d.hidden % 192 == 0 && d.inter % 192 == 0 &&
-           (long)b->B * 4 <= (long)b->B * (b->Lt + b->Li);
+    return g_wgrad_tn && d.dtype == CPT_BF16 && b->n_rows == 0 && d.layers >= 1 && d.hidden % 192 == 0 && d.inter % 192 == 0 &&
+           (long)b->B * 4 <= (long)b->B * (b->Lt + b->Li) && !(b->mask_3d && b->attn_mask);
 }
 
 // queue a column-sum job behind the ones already waiting for a carrier launch; a full queue first goes out on a launch of its own, so no
@@ -291,7 +268,7 @@ static int train_fwd_impl(const cpt_model* m, const cpt_rel2* x, const cpt_batch
     if (L > 288) return abi_fail(CPT_ERR_SHAPE, "cpt_train_fwd: sequence length %d > 288", L);
     const int m3d = (b->mask_3d && b->attn_mask) ? 1 : 0;
     const bool x3_attn = train_x3_attention(d, L, m3d);
-    const bool tail = train_tail_on(d, b) && !m3d;
+    const bool tail = train_tail_on(d, b);
     if (!x3_attn && !cpt::attention_bwd_supported(dt, L, pa ? 1 : 0, m3d))       // reject here, not after the forward has run (the backward's attention kernel sets the limit)
     {
         int lmax = L;
@@ -598,7 +575,7 @@ static int train_bwd_impl(const cpt_model* m, const cpt_rel2* x, const cpt_batch
     void* duh_lp = ws + w.duh_lp;
     float* drows = (float*)(ws + w.drows);
     const bool nsp = !m->w_tr && !m->w_dec;
-    const bool tail = train_tail_on(d, b) && !(b->mask_3d && b->attn_mask);      // the forward's pruned last layer (same predicate)
+    const bool tail = train_tail_on(d, b);      // the forward's pruned last layer (same predicate)
     const int Rh = (!nsp && b->n_rows > 0) ? b->n_rows : B;      // head rows (see cpt_train_fwd)
     if (x && !nsp) return abi_fail(CPT_ERR_NULL, "cpt_train_bwd_rel2: the model needs the pooler and head 0 (w_pool, w_rel) and no MLM head");
     if (nsp) {

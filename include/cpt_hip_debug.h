@@ -2,7 +2,7 @@
  *
  * Exported by the same library; NOT part of the hot-path interface of cpt_hip.h.  bench.py's roofline leg uses the per-kernel event
  * timing; tools/ and the A/B tests use cpt_set_tuning and the per-workgroup trace.  A product host never needs to call any of them.
- * Round 5: the kernel-variant switches are process-global state only in the DEVELOPMENT build of the library (-DCPT_ABLATION,
+ * The kernel-variant switches are process-global state only in the DEVELOPMENT build of the library (-DCPT_ABLATION,
  * cpt_amd/libcpt_hip_abl.so, selected by CPT_AMD_ABLATION=1); in the product build they are compile-time constants, the code behind the
  * losing settings is not compiled, and cpt_set_tuning refuses every key but -1 (cpt_build_info tells the two apart).
  */
@@ -42,81 +42,58 @@ int cpt_gemm_ln_prod3_panel_waves(int waves, const void* A_panel, const void* W_
  * bit 0 set = the CPT_ABLATION development build (libcpt_hip_abl.so), where the switches are process-global (round 5). */
 int cpt_build_info(void);
 
-/* Kernel-variant switches for A/B measurements (CPT_ABLATION build only); defaults are the shipped configuration.
- *   key 0  GEMM (20 / 21: force the two-pass / the 4-wave LayerNorm-consumer kernel where legal): 0 = generic register-staged kernel only; 3 (default) = pipelined LDS-DMA kernel, tile shape chosen
- *          per GEMM; fixed shapes 13 = 128x192 (3-stage), 11 = 192x192, 10 = 128x384, 14 = 384x192,
- *          15 = 128x192 two workgroups per CU, 18 = 64x192 (small M)
- *   key 1  GEMM ablation bits: 1 no operand LDS-DMA, 2 no fragment reads, 4 no MFMA, 8 no epilogue,
- *          32 fused QKV + attention kernel without its attention phase
- *   key 2  attention backward: 0 = generic fp32-math kernel, 1 (default) = MFMA kernel for bf16, L <= 128
- *   key 3  split-K target for the generic path
- *   key 4  1 = bf16 residual stream in the kernel-per-op bf16 encoder (default 0: fp32 residual)
- *   key 5  0 = run the encoder LayerNorms as kernels even when cpt_model.fold is given (default 1: folded)
- *   key 6  QKV projection + attention: 0 = two kernels, 1 = fused, one workgroup per (sequence, head), two per CU,
- *          2 = the same, one per CU, 3 (default) = fused, one workgroup per (sequence, three heads) where heads % 3 == 0,
- *          else 1 (bf16, L <= 128 only; otherwise always two kernels)
- *   key 9  residual stream of the fused bf16 encoder: 1 (default) = 3-byte form (cpt_gemm_ln_prod3), 0 = fp32 + bf16 copies
- *   key 10 bf16 weight gradients of cpt_train_bwd: 1 (default) = TN GEMM (operands read as stored, split-K partials reduced in
- *          order), 0 = explicit operand transposes + NT GEMM
- *   key 11 fused QKV + attention, form 3: 1 (default) = read cpt_layer_fold.w_qkv_t when given, 0 = always the row-major weight
- *   key 12 FFN-up two-pass kernel: 1 (default) = refill DMA issued behind the first k-step after the barrier, 0 = right behind it
- *   key 13 timing experiments of the panel producer (gemm_prod.hip); 0 (default) = the shipped kernel
- *   key 14 panel mode of the fused bf16 encoder: 1 (default) = ctx / FFN activation in the fragment-major panel layout where shapes allow
- *          (cpt_gemm_ln_prod3_panel), 0 = row-major tensors (cpt_gemm_ln_prod3)
- *   key 15 panel mode: 1 (default) = launches that leave CUs idle carry 16 workgroups that read the next launch's weights into the
- *          Infinity Cache, 0 = no prefetch workgroups
- *   key 16 FFN-up two-pass kernel (and with it panel mode) from this many 384 x 256 tiles on (default 192; experiments with small batches)
- *   key 17 LayerNorm backward, two-stage column-sum form: rows per workgroup (default 0 = 8 from 2048 rows on, else 4; experiments)
- *   key 18 training backward, bias-gradient column sums inside their producers: bit 0 = b_in in the GELU-gradient epilogue (round 6: as partial rows that a
- *          later LayerNorm-backward launch adds up in spare workgroups), bit 1 = b_qkv in the attention backward kernel (default 3); a cleared bit runs the
- *          stand-alone column-sum launch
- *   key 19 training backward, a layer's weight gradients: 2 (default) = FFN down | FFN up | attention output in one launch + Q|K|V alone where the
- *          shapes fit one round (else as 1), 1 = two paired launches (the two FFN matrices; attention output + Q|K|V), 0 = four launches with
- *          their own split-K reductions
- *   key 20 stand-alone QKV projection with the LayerNorm folded (sequences longer than 128: attention runs as its own kernel): 1 (default) =
- *          the GELU-less form of the two-pass 384 x 256 kernel when its tiles fill the chip, 0 = the 384 x 192 pipelined kernel
- *   key 21 stand-alone attention kernel, sequences longer than 128: 1 (default) = the 128-query tiles of a (sequence, head) are neighbouring
- *          workgroups of one XCD (their shared K / V rows are fetched from memory once), 0 = the (pair, tile) grid
- *   key 22 training forward, FFN-down at 2048..6144 rows: 1 (default) = 128 x 192 tiles with K split over two workgroups, the two partial
- *          matrices added by the dropout + residual + LayerNorm pass behind it; 0 = 64 x 192 tiles over the whole K
- *   key 23 bf16x3 parity mode: 1 (default) = the FFN-up's GELU epilogue writes the split copy of its output that the FFN-down reads, 0 = an
- *          fp32 tensor and a stand-alone cpt_split3 pass
- *   key 24 wave shape of the panel LayerNorm producers' 128 x 192 tile (gemm_prod.hip; same bits either way): 0 (default) = by shape -- 4 x 1 waves of
- *          32 x 192 with the operand stream interleaved between the MFMAs when the tiles run several rounds, else 4 x 2 waves of 32 x 96 (in one
- *          round the denser 4-wave launch takes clock from its neighbours under the power cap: no gain for the step); 4 / 8 force one shape
- *   key 25 fused bf16 encoder: 1 (default) = text embedding and region-feature pad + cast in ONE launch, 0 = two launches
- *   key 26 MLM head on the [MASK] rows: percent of the decoder weight table prefetched by the gather + LayerNorm launch (default 40; the rest rides
- *          on the reduce + GELU + LayerNorm launch; 100 = round 3's form)
- *   key 27 bf16x3 parity mode: 1 (default) = attention on bf16 MFMA with split operands (three-term products), ctx written as the split copy the
- *          attention-output GEMM reads; 0 = the fp32 MFMA attention kernel and a cpt_split3 pass over ctx
- *   key 28 panel layout of the FFN activation when the producers run several rounds of tiles: 1 (default), 0 = row-major there (round 3)
- *   key 29 the 4-wave 192 x 256 LayerNorm-consumer kernel with the operand stream between the MFMAs (gemm_ffn4.hip) in place of the two-pass
- *          384 x 256 kernel (gemm_ffn.hip): 1 (default) = where its tiles fill their rounds at least 10 % better (Oscar-large FFN-up), 2 = wherever
- *          legal, 0 = nowhere; same bits
- *   key 30 fused bf16 encoder at the full-panel shapes: 1 (default) = the residual stream itself in the panel layout and the LayerNorm producers'
- *          register-direct epilogue (cpt_gemm_ln_prod3_rpanel), 0 = row-major 3-byte stream + slab epilogue (round 3); same bits
- *   key 31 fused bf16 encoder, only the [MASK] rows (or only the [CLS] rows) read behind it: 1 (default) = the last layer's attention output, FFN and
- *          LayerNorms on those rows alone (rowops.hip tail_rows / tail_finish, gemm.hip gemm_rows_split), 0 = every row through the last layer;
- *          same values to bf16 accuracy, not the same bits (different kernels behind the last attention)
- *   key 32 fused bf16 encoder, batches whose row count the full panel mode does not take: 1 (default) = the encoder's tensors are sized and launched for the
- *          next row count it takes (at most 1.5x the real rows; the padded rows belong to no sequence), 0 = such batches run the row-major kernels; same bits
- *   key 33 training step, last encoder layer: 1 (default) = everything behind its attention (attention output, FFN, both LayerNorms; forward and backward) on
- *          the head's rows only -- one per sequence ([MASK], or [CLS] for the NSP head) -- when the batch carries no label grid; 0 = all rows
- *   key 34 training backward, data-gradient GEMMs in front of a LayerNorm backward at 2048..6144 rows: 1 (default) = 128 x 192 tiles with K split over two
- *          workgroups, two BF16 partial matrices added (with the fp32 residual) by the LayerNorm backward; 0 = 64 x 192 tiles over the whole K, fp32 out
- *   key 35 training backward, the GELU-gradient data-gradient GEMM (FFN-down): 1 (default) = 256 x 192 tiles where 128-row tiles would make between one and two
- *          rounds of workgroups and 256-row tiles at most one (M = 3840: 240 instead of 480 workgroups), 0 = 128 x 192 tiles
- *   key 36 training forward with hidden dropout: 1 (default) = the LayerNorm launches write no fp32 output, the row pass behind re-forms the residual it adds
- *          from the pre-LayerNorm rows kept for the backward (+ (mean, rstd), gain, shift); 0 = fp32 outputs written and read back
- *   key 37 training backward: 1 (default) = the K-split partial matrices of a layer's Q|K|V weight gradient are added up by the workgroups the NEXT layer's
- *          three-problem weight-gradient launch leaves idle (216 of 256 CUs busy at hidden 768); 0 = a reduction launch of their own
- *   key 38 attention backward with the forward's statistics (bf16 training step, L <= 128): 1 (default) = where two workgroups per (sequence, head) still fit
- *          one per CU (2 B heads <= 256: 4 sequences per GPU) the two phases (dQ | dK, dV) run in a workgroup each, side by side; 0 = one workgroup runs both
- *   key 39 training step at few rows (4 sequences per GPU): 1 (default) = the FFN-up forward (u and gelu(u) out) on 64 x 96 tiles and the GELU-gradient
- *          data-gradient GEMM on 64 x 128 tiles where 64 x 192 tiles fill at most half the chip (also: forward Q|K|V and attention output on 64 x 96, the
- *          attention output's data gradient on 64 x 64, the unsplit TN weight gradient on 64 x 192); 0 = 64 x 192 / 128 x 192 tiles; v > 1 = the
- *          workgroup-count threshold itself instead of 128 (256 at 32 sequences: 5.315 / 5.307 vs 5.321 / 5.316 ms -- nothing, the default stays 128)
- *   key -1 restores the default of every key (value ignored) */
+/* Kernel-variant switches for A/B measurements (CPT_ABLATION build only); defaults are the shipped configuration.  The AUTHORITATIVE list is the
+ * table in cpt_amd/csrc/switches.h (key, variable, default, legal range, description): the library's declarations, this call's lookup and its
+ * reset are generated from it, and tests/test_abi_cpu.py holds the list below to the same keys.  A value outside a key's range is clamped into it.
+ * Switches are process-global: they must NOT change between a training forward (cpt_train_fwd*) and its backward (cpt_train_bwd*) -- both
+ * derive the step's launches and buffers from them, and the backward reads what the forward wrote.  Set them before a step, restore them after.
+ *   key 0  (default 3) GEMM tile: 3 = by shape; 0 = generic register-staged kernel; a tile id of cpt_gemm_tile forces that tile where legal
+ *   key 1  (default 0) knock-out bits of the pipelined GEMMs (1 no operand DMA, 2 no fragment reads, 4 no MFMA, 8 no epilogue) and of the fused QKV + attention
+ *          kernel (32 no attention phase); results are garbage unless 0
+ *   key 2  (default 1) attention backward, bf16: 1 = transpose-read MFMA kernels (L <= 288); 0 = generic kernel always; 2 = L <= 128 through the older MFMA
+ *          kernel with transposed tile copies
+ *   key 3  (default 384) generic GEMM path: workgroup count the split-K factor aims at
+ *   key 6  (default 3) bf16, L <= 128: QKV projection + attention in one kernel (0 = two kernels; 1 = one workgroup per (sequence, head), two per CU; 2 = same,
+ *          one per CU; 3 = one workgroup per (sequence, three heads) where heads % 3 == 0, else 1)
+ *   key 9  (default 1) fused bf16 encoder: residual stream in the 3-byte form (bf16 hi + int8 lo); 0 = fp32 + bf16 copies
+ *   key 10 (default 1) training backward: bf16 weight gradients through the TN GEMM (operands read as stored, split-K partials reduced in order); 0 = explicit
+ *          operand transposes + NT GEMM
+ *   key 13 (default 0) knock-out experiments of the panel producer (gemm_prod.hip prod3_panel_kernel: 1 half the A loads, 2 no A loads, 3 no W DMA, ...); results
+ *          are garbage unless 0
+ *   key 14 (default 1) fused bf16 encoder: ctx and the FFN activation in the fragment-major panel layout where the shapes allow (gemm_prod.hip); 0 = row-major
+ *          tensors
+ *   key 16 (default 192) FFN-up two-pass kernel (and with it panel mode) from this many 384 x 256 tiles on
+ *   key 17 (default 0) LayerNorm backward, two-stage column-sum form: rows per workgroup (0 = 8 from 2048 rows on, else 4 = one row per wave)
+ *   key 18 (default 3) training backward, bias-gradient column sums inside their producers: bit 0 = b_in (GELU-gradient epilogue), bit 1 = b_qkv (attention
+ *          backward); a cleared bit runs the stand-alone column-sum launch
+ *   key 19 (default 2) training backward, a layer's weight gradients: 2 = FFN down | FFN up | attention output in one launch + Q|K|V alone where the shapes fit
+ *          one round (else as 1), 1 = two paired launches, 0 = four single launches
+ *   key 20 (default 1) stand-alone LayerNorm-consumer QKV projection: the GELU-less two-pass 384 x 256 kernel when its tiles fill the chip; 0 = the 384 x 192
+ *          pipelined kernel
+ *   key 22 (default 1) training forward, FFN-down at 2048..6144 rows: 128 x 192 tiles with K split over two workgroups, partial matrices summed by the LayerNorm
+ *          pass; 0 = 64 x 192 tiles over the whole K
+ *   key 24 (default 0) wave shape of the panel LayerNorm producers' 128 x 192 tile: 0 = by shape (4 when the tiles run several rounds), 4 = 4 x 1 waves of 32 x
+ *          192, 8 = 4 x 2 waves of 32 x 96; same bits
+ *   key 25 (default 1) fused bf16 encoder: text embedding + region-feature pad/cast in one launch; 0 = two launches
+ *   key 26 (default 40) MLM head on the [MASK] rows: percent of the decoder table prefetched by the head's first launch (the rest: by its reduce + GELU +
+ *          LayerNorm launch)
+ *   key 27 (default 1) bf16x3 parity mode: attention on bf16 MFMA with split operands; 0 = the fp32 MFMA kernel + a split3 pass over ctx
+ *   key 28 (default 1) panel layout for the FFN activation also when the producers run several rounds of tiles; 0 = row-major there
+ *   key 29 (default 1) 4-wave 192 x 256 LayerNorm-consumer kernel (gemm_ffn4.hip) in place of the two-pass 384 x 256 kernel: 1 = where its tiles fill their
+ *          rounds at least 10 % better, 2 = wherever legal, 0 = nowhere; same bits
+ *   key 30 (default 1) fused bf16 encoder at the full-panel shapes: the residual stream itself in the panel layout, register-direct producer epilogue
+ *          (gemm_prod.hip RP); 0 = row-major 3-byte stream; same bits
+ *   key 31 (default 1) only [MASK] (or only [CLS]) rows read behind the encoder: the last layer's attention output / FFN / LayerNorms on those rows alone; 0 =
+ *          every row
+ *   key 34 (default 1) training backward, data-gradient GEMMs in front of a LayerNorm backward at 2048..6144 rows: two K-split bf16 partial matrices of 128 x 192
+ *          tiles; 0 = 64 x 192 tiles over the whole K, fp32 out
+ *   key 36 (default 1) training forward with hidden dropout: LayerNorm launches write no fp32 output, the next row pass re-forms the residual; 0 = fp32 outputs
+ *          written and read back
+ *   key 37 (default 1) training backward: Q|K|V weight-gradient partial sums added up inside the next layer's three-problem weight-gradient launch; 0 = a
+ *          reduction launch of their own
+ * Two more calls that are not switches: cpt_set_tuning(-1, 0) restores the default of every key above (and the trace filter);
+ * cpt_set_tuning(8, epilogue_id | K << 8) narrows cpt_debug_gemm_trace to the launches of one epilogue id / one K (255: all).
+ * Any other key fails with CPT_ERR_SHAPE; the product build refuses every key but -1. */
 int cpt_set_tuning(int key, int value);
 /* Debug: when buf != NULL the pipelined GEMM writes 8 int64 per workgroup (shader-clock stamps at
  * start / after prologue issue / after K loop / after staging / end, and the XCC id). */

@@ -54,3 +54,26 @@ def test_product_path_has_no_cpu_fallback():
             if f.endswith(".py"):
                 txt = open(os.path.join(dp, f)).read()
                 assert "oracle" not in txt.replace("# noqa", ""), "%s mentions the oracle" % f
+
+
+def test_switch_table_and_header_key_list_agree():
+    """The kernel-variant switches are written down once, in the table of cpt_amd/csrc/switches.h; the comment of cpt_set_tuning in
+    include/cpt_hip_debug.h describes the same keys to a caller.  Both name every key exactly once, and no source file defines a switch
+    of its own beside the table."""
+    csrc = os.path.join(ROOT, "cpt_amd", "csrc")
+    table = open(os.path.join(csrc, "switches.h")).read()
+    rows = re.findall(r"^\s*X\(\s*(-?\d+)\s*,\s*(\w+)\s*,", table, flags=re.M)
+    keys = [int(k) for k, _ in rows]
+    names = [n for _, n in rows]
+    assert len(keys) >= 10
+    assert len(set(keys)) == len(keys), "a key appears twice in the switch table: %s" % sorted(k for k in keys if keys.count(k) > 1)
+    assert len(set(names)) == len(names), "a variable appears twice in the switch table"
+    assert all(k >= 0 and k != 8 for k in keys), "-1 (reset) and 8 (trace filter) are not switches"
+    header = open(os.path.join(ROOT, "include", "cpt_hip_debug.h")).read()
+    doc = [int(k) for k in re.findall(r"^ \*\s+key\s+(-?\d+)\b", header, flags=re.M)]
+    assert len(set(doc)) == len(doc), "a key is described twice in cpt_hip_debug.h: %s" % sorted(k for k in doc if doc.count(k) > 1)
+    assert sorted(doc) == sorted(keys), "switches.h and cpt_hip_debug.h disagree on keys %s" % sorted(set(doc) ^ set(keys))
+    assert "switches.h" in header                      # the header says which file is authoritative
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".hip") or f.endswith(".cpp"):
+            assert "CPT_SWITCH(" not in open(os.path.join(csrc, f)).read(), "%s defines a switch outside the table" % f

@@ -286,6 +286,8 @@ def test_round4_kernel_choices_are_bit_identical(dev):
                 got = run()
                 L.check(L.lib().cpt_set_tuning(-1, 0))
                 assert torch.equal(got, ref), "B = %d: cpt_set_tuning(%d, %d) changes the logits" % (B, key, v)
+        # the reset itself (a loop over the switch table): behind the last cpt_set_tuning(-1, 0) the library runs its shipped configuration again
+        assert torch.equal(run(), ref), "B = %d: the logits after cpt_set_tuning(-1, 0) differ from the shipped configuration's" % B
 
 
 @pytest.mark.ablation

@@ -1,5 +1,5 @@
 """Per-CU timeline of the pipelined GEMM's workgroups (CPT_ABLATION build: shader-clock stamps + HW_ID).  GPU box only.
-usage: python tools/gemm_cu_timeline.py <variant> <shape> [skew]      (shape: qkv|attn_out|ffn_up|ffn_down)
+usage: python tools/gemm_cu_timeline.py <variant> <shape>      (shape: qkv|attn_out|ffn_up|ffn_down)
 Shows which workgroups share a CU and how their K-loop / epilogue phases overlap."""
 import os
 import sys
@@ -16,7 +16,6 @@ M, H, I = 64 * 120, 768, 3072
 shapes = {"qkv": (M, 3 * H, H, L.EPI_NONE, dt), "attn_out": (M, H, H, L.EPI_RESID, torch.float32),
           "ffn_up": (M, I, H, L.EPI_GELU, dt), "ffn_down": (M, H, I, L.EPI_RESID, torch.float32)}
 variant, name = int(sys.argv[1]), sys.argv[2]
-skew = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 abl = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 buf = torch.zeros(4096 * 8, device=dev, dtype=torch.int64)
 if name.startswith("model:"):
@@ -31,7 +30,6 @@ if name.startswith("model:"):
     model.to(dev).eval().set_compute_dtype("bf16")
     bt = {k: v.to(dev) for k, v in synth.make_batch(64, cfg, seed=88).items()}
     L.check(L.lib().cpt_set_tuning(0, variant))
-    L.check(L.lib().cpt_set_tuning(7, skew))
 
     def fwd():
         with torch.no_grad():
@@ -54,7 +52,6 @@ else:
     b = torch.randn(n, device=dev)
     r = torch.randn(m, n, device=dev) if epi == L.EPI_RESID else None
     L.check(L.lib().cpt_set_tuning(0, variant))
-    L.check(L.lib().cpt_set_tuning(7, skew))
     for _ in range(3):
         ops.gemm(x, w, b, epi=epi, resid=r, out_dtype=odt)
     L.lib().cpt_debug_gemm_trace(buf.data_ptr())
@@ -62,7 +59,6 @@ else:
     torch.cuda.synchronize()
     L.lib().cpt_debug_gemm_trace(None)
 L.check(L.lib().cpt_set_tuning(0, 3))
-L.check(L.lib().cpt_set_tuning(7, 0))
 t = buf.cpu().numpy().reshape(-1, 8)
 print("debug counter (last trace slot):", int(t[-1, 7]))
 t[-1, :] = 0
@@ -76,7 +72,7 @@ if os.environ.get("CPT_TRACE_SUMS"):
 hw, xcc, bid = t[:, 5], t[:, 6] & 15, t[:, 7]
 cu = ((hw >> 8) & 15) | (((hw >> 12) & 1) << 4) | (((hw >> 13) & 7) << 5) | (xcc << 8)
 print("abl %d " % abl, end="")
-print("%s variant %d skew %d: %d workgroups on %d distinct CUs (xcc values %s)" % (name, variant, skew, len(t), len(set(cu.tolist())), sorted(set(xcc.tolist()))))
+print("%s variant %d: %d workgroups on %d distinct CUs (xcc values %s)" % (name, variant, len(t), len(set(cu.tolist())), sorted(set(xcc.tolist()))))
 both_k = one_k = both_e = 0
 shown = 0
 for c in sorted(set(cu.tolist())):
