@@ -15,7 +15,6 @@
     X( 2, g_attn_bwd_variant,    1,   0,   2, "attention backward, bf16: 1 = transpose-read MFMA kernels (L <= 288); 0 = generic kernel always; 2 = L <= 128 through the older MFMA kernel with transposed tile copies") \
     X( 3, g_splitk_target,     384,   1, 0x7fffffff, "generic GEMM path: workgroup count the split-K factor aims at") \
     X( 6, g_fuse_attn,           3,   0,   3, "bf16, L <= 128: QKV projection + attention in one kernel (0 = two kernels; 1 = one workgroup per (sequence, head), two per CU; 2 = same, one per CU; 3 = one workgroup per (sequence, three heads) where heads % 3 == 0, else 1)") \
-    X( 9, g_resid3,              1,   0,   1, "fused bf16 encoder: residual stream in the 3-byte form (bf16 hi + int8 lo); 0 = fp32 + bf16 copies") \
     X(10, g_wgrad_tn,            1,   0,   1, "training backward: bf16 weight gradients through the TN GEMM (operands read as stored, split-K partials reduced in order); 0 = explicit operand transposes + NT GEMM") \
     X(13, g_prod_abl,            0,   0,   4, "knock-out experiments of the panel producer (gemm_prod.hip prod3_panel_kernel: 1 half the A loads, 2 no A loads, 3 no W DMA, ...); results are garbage unless 0") \
     X(14, g_panel,               1,   0,   1, "fused bf16 encoder: ctx and the FFN activation in the fragment-major panel layout where the shapes allow (gemm_prod.hip); 0 = row-major tensors") \

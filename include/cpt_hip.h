@@ -470,8 +470,8 @@ int cpt_gemm_ln_prod(const void* A_bf16, int lda, const void* W_bf16, int ldw, c
                      const float* st_in, const float* g_in, const float* b_in, float eps, int hidden, float* out_f32,
                      void* out_bf16, float* st_out, int ldo, int M, int N, int K, void* stream);
 
-/* The producer with the residual stream in the 3-byte form (round 2; cpt_model_fwd's default in bf16 mode, cpt_set_tuning(9, 0)
- * restores the fp32 + bf16 pair): a pre-LayerNorm sum x travels as T = its fp32 pattern rounded to 24 bits (round half away),
+/* The producer with the residual stream in the 3-byte form (round 2; the form cpt_model_fwd's LayerNorm-folded bf16 encoder runs in;
+ * cpt_gemm_ln_prod above is its fp32 + bf16 reference): a pre-LayerNorm sum x travels as T = its fp32 pattern rounded to 24 bits (round half away),
  * hi = (T + 0x80) >> 8 as a plain bf16 tensor (the next GEMM's A operand) and lo = the signed byte T - (hi << 8);
  * x' = ((hi << 8) + lo) << 8, |x' - x| <= 2^-17 |x|.  3 + 3 bytes per element through the epilogue instead of 4 + 6.
  *   cpt_gemm_ln_prod3: as cpt_gemm_ln_prod with resid = (resid_hi bf16, resid_lo int8) [M][ldr], out = (out_hi bf16, out_lo int8) [M][ldo]

@@ -55,7 +55,6 @@ int cpt_build_info(void);
  *   key 3  (default 384) generic GEMM path: workgroup count the split-K factor aims at
  *   key 6  (default 3) bf16, L <= 128: QKV projection + attention in one kernel (0 = two kernels; 1 = one workgroup per (sequence, head), two per CU; 2 = same,
  *          one per CU; 3 = one workgroup per (sequence, three heads) where heads % 3 == 0, else 1)
- *   key 9  (default 1) fused bf16 encoder: residual stream in the 3-byte form (bf16 hi + int8 lo); 0 = fp32 + bf16 copies
  *   key 10 (default 1) training backward: bf16 weight gradients through the TN GEMM (operands read as stored, split-K partials reduced in order); 0 = explicit
  *          operand transposes + NT GEMM
  *   key 13 (default 0) knock-out experiments of the panel producer (gemm_prod.hip prod3_panel_kernel: 1 half the A loads, 2 no A loads, 3 no W DMA, ...); results
