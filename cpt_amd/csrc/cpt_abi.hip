@@ -578,9 +578,10 @@ struct Fwd {
             if (p.img_split2) TRY(cpt::gemm_img_proj(imgp, d.img_dim_pad, m->w_img, d.img_dim_pad, m->b_img, pre, H, B * Li, H, d.img_dim_pad, s), "gemm(img_embedding, split K)");
             else TRY(gm(CPT_EPI_NONE, imgp, d.img_dim_pad, m->w_img, d.img_dim_pad, m->b_img, nullptr, 0, pre, CPT_F32, H, B * Li, H), "gemm(img_embedding)");
             const bool iln = d.use_img_ln && m->img_ln_g;
+            cpt::LnRowsExtra e;
+            e.resid = p.img_split2 ? pre + (size_t)B * Li * H : nullptr; e.out_lo = fold ? x_lo() : nullptr; e.out_panel = p.rpanel;
             TRY(cpt::layernorm_rows_ex(pre, iln ? m->img_ln_g : nullptr, iln ? m->img_ln_b : nullptr, d.img_ln_eps, fold ? nullptr : x_f32,
-                                       lp ? x_lp : nullptr, dt, B * Li, H, Li, L, Lt, 0, s, p.img_split2 ? pre + (size_t)B * Li * H : nullptr, nullptr, nullptr,
-                                       fold ? x_lo() : nullptr, 1, 0, p.rpanel), "layernorm(img)");
+                                       lp ? x_lp : nullptr, dt, B * Li, H, Li, L, Lt, 0, s, &e), "layernorm(img)");
         }
         return CPT_OK;
     }

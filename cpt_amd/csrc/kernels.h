@@ -130,12 +130,24 @@ int dropout_rows(const float* x, const float* resid, float* y, void* y_lp, int l
 int dropout_mask(int kind, unsigned char* out, int n0, int n1, int n2, const DropSpec& d, hipStream_t s);
 int adamw_flat(float* p, const float* g, float* m, float* v, const unsigned char* code, void* shadow_bf16, size_t n,
                double lr, double beta1, double beta2, double eps, double wd, int step, float grad_scale, hipStream_t s, int flags = 0);     // flags: CPT_ADAMW_* (cpt_hip.h)
+// everything optional of layernorm_rows_ex (NULL: none of it)
+struct LnRowsExtra {
+    const float* resid = nullptr;       // resid / drop / pre_out: normalise dropout(x) + resid (element index row * H + col of the hidden-site mask) and store that sum
+    const DropSpec* drop = nullptr;
+    float* pre_out = nullptr;
+    void* out_lo = nullptr;             // rows leave in the 3-byte residual form (hi -> out_lp)
+    int x_parts = 1;                    // > 1: x holds that many split-K partial matrices, x_stride elements apart; the row processed is their sum in split order
+    size_t x_stride = 0;
+    int out_panel = 0;                  // round 5, with out_lo: out_lp / out_lo are the bases of the panel-layout residual stream
+    float* stat_out = nullptr;          // round 6: [R][2] (mean, rstd) of every row, for ln_bwd
+    const RowMap* drop_rows = nullptr;  // dropout masks taken at these rows of the full tensor (compact head rows)
+    unsigned short* keep_out = nullptr; // round 6, with drop: [R][64] keep bits of the row's dropout mask for ln_bwd (LnBwdExtra::keep_bits)
+    // round 6: resid = the pre-LayerNorm rows of the LayerNorm in front, whose output is re-formed here from its [R][2] (mean, rstd), gain and shift (that launch then skips its fp32 output)
+    const float *resid_stat = nullptr, *resid_g = nullptr, *resid_b = nullptr;
+    const DropSpec* out_drop = nullptr; // round 6: hidden dropout on the OUTPUT rows, element index (output row) * H + col
+};
 int layernorm_rows_ex(const float* x, const float* g, const float* bta, float eps, float* out_f32, void* out_lp,
-                      int lp_dtype, int R, int H, int grp, int grp_stride, int grp_off, int gelu_in, hipStream_t s,
-                      const float* resid = nullptr, const DropSpec* drop = nullptr, float* pre_out = nullptr, void* out_lo = nullptr,
-                      int x_parts = 1, size_t x_stride = 0, int out_panel = 0, float* stat_out = nullptr, const RowMap* drop_rows = nullptr,
-                      unsigned short* keep_out = nullptr, const float* resid_stat = nullptr, const float* resid_g = nullptr, const float* resid_b = nullptr, const DropSpec* out_drop = nullptr);     // out_drop (round 6): hidden dropout on the OUTPUT rows, element index (output row) * H + col;     // resid_stat / resid_g / resid_b (round 6): resid = the pre-LayerNorm rows of the LayerNorm in front, whose output is re-formed here from its [R][2] (mean, rstd), gain and shift (that launch then skips its fp32 output);   keep_out (round 6, with drop): [R][64] keep bits of the row's dropout mask for ln_bwd (LnBwdExtra::keep_bits)     // stat_out (round 6): [R][2] (mean, rstd) of every row, for ln_bwd     // out_panel (round 5, with out_lo): out_lp / out_lo are the bases of the panel-layout residual stream; x_parts > 1: x holds that many split-K partial matrices, x_stride elements apart; the row processed is their sum in split order
-// resid / drop / pre_out: normalise dropout(x) + resid (element index row * H + col of the hidden-site mask) and store that sum
+                      int lp_dtype, int R, int H, int grp, int grp_stride, int grp_off, int gelu_in, hipStream_t s, const LnRowsExtra* ext = nullptr);
 
 // out[M][N] fp32 = sum_k A[k][m] W[k][n]: bf16 operands with the contraction index as the slow dimension (weight gradients
 // without operand transposes); needs gemm_tn_eligible; `partials` (optional) holds the split-K partial matrices

@@ -228,28 +228,28 @@ __global__ __launch_bounds__(ROW_THREADS) void layernorm768_kernel(const float* 
 
 int layernorm_rows_ex(const float* x, const float* g, const float* bta, float eps, float* out_f32,
                       void* out_lp, int lp_dtype, int R, int H, int grp, int grp_stride, int grp_off,
-                      int gelu_in, hipStream_t s, const float* resid, const DropSpec* drop, float* pre_out, void* out_lo, int x_parts, size_t x_stride, int out_panel, float* stat_out, const RowMap* drop_rows, unsigned short* keep_out,
-                      const float* resid_stat, const float* resid_g, const float* resid_b, const DropSpec* out_drop) {
-    if (x_parts < 1 || x_parts > 64) return CPT_ERR_SHAPE;
-    const DropSpec odr = out_drop ? *out_drop : DropSpec{};
-    if (odr.thresh != 0 && out_panel) return CPT_ERR_SHAPE;
-    if (resid_stat && !(resid && resid_g && resid_b)) return CPT_ERR_NULL;
-    if (out_panel && (!out_lo || out_f32 || H % 16)) return CPT_ERR_SHAPE;      // panel output: the 3-byte residual stream only (rows rounded up to 32 by the caller's buffer)
-    if (out_lo && !(out_lp && lp_dtype == CPT_BF16)) return CPT_ERR_DTYPE;
+                      int gelu_in, hipStream_t s, const LnRowsExtra* ext) {
+    const LnRowsExtra e = ext ? *ext : LnRowsExtra{};
+    if (e.x_parts < 1 || e.x_parts > 64) return CPT_ERR_SHAPE;
+    const DropSpec odr = e.out_drop ? *e.out_drop : DropSpec{};
+    if (odr.thresh != 0 && e.out_panel) return CPT_ERR_SHAPE;
+    if (e.resid_stat && !(e.resid && e.resid_g && e.resid_b)) return CPT_ERR_NULL;
+    if (e.out_panel && (!e.out_lo || out_f32 || H % 16)) return CPT_ERR_SHAPE;      // panel output: the 3-byte residual stream only (rows rounded up to 32 by the caller's buffer)
+    if (e.out_lo && !(out_lp && lp_dtype == CPT_BF16)) return CPT_ERR_DTYPE;
     if (R <= 0 || H <= 0 || H % 4 || H > 256 * MAXV || grp <= 0) return CPT_ERR_SHAPE;
     if (!x || (!out_f32 && !out_lp)) return CPT_ERR_NULL;
-    const DropSpec dr = drop ? *drop : DropSpec{};
-    const RowMap drows = drop_rows ? *drop_rows : RowMap{nullptr, 0, 0};
+    const DropSpec dr = e.drop ? *e.drop : DropSpec{};
+    const RowMap drows = e.drop_rows ? *e.drop_rows : RowMap{nullptr, 0, 0};
     if (grp_stride == 0 && grp != R) grp_stride = grp;
     // H = 768 rows without residual / dropout / GELU / split-K partials: the lean kernel, one row per wave (measured against two and four rows per wave:
     // profiles/r05_ab_log.md -- 0.59 / 0.72 of 8 TB/s at 7680 / 61440 rows for the bf16 output against 0.58 / 0.71 and 0.49 / 0.67; the general kernel: 0.56 / 0.55)
-    if (keep_out && dr.thresh == 0) keep_out = nullptr;
-    if (H == 768 && !gelu_in && !resid && dr.thresh == 0 && !pre_out && x_parts == 1 && !stat_out && odr.thresh == 0) {
+    unsigned short* keep_out = dr.thresh != 0 ? e.keep_out : nullptr;
+    if (H == 768 && !gelu_in && !e.resid && dr.thresh == 0 && !e.pre_out && e.x_parts == 1 && !e.stat_out && odr.thresh == 0) {
         dim3 g768((R + 3) / 4), b768(ROW_THREADS);
         if (out_lp && lp_dtype == CPT_BF16)
-            layernorm768_kernel<bf16, 1><<<g768, b768, 0, s>>>(x, g, bta, eps, out_f32, (bf16*)out_lp, R, grp, grp_stride, grp_off, (signed char*)out_lo, out_panel);
+            layernorm768_kernel<bf16, 1><<<g768, b768, 0, s>>>(x, g, bta, eps, out_f32, (bf16*)out_lp, R, grp, grp_stride, grp_off, (signed char*)e.out_lo, e.out_panel);
         else
-            layernorm768_kernel<float, 1><<<g768, b768, 0, s>>>(x, g, bta, eps, out_f32, (float*)out_lp, R, grp, grp_stride, grp_off, (signed char*)out_lo, out_panel);
+            layernorm768_kernel<float, 1><<<g768, b768, 0, s>>>(x, g, bta, eps, out_f32, (float*)out_lp, R, grp, grp_stride, grp_off, (signed char*)e.out_lo, e.out_panel);
         return CPT_OK;
     }
     const int rpw = R >= 24576 ? 2 : 1;
@@ -257,9 +257,9 @@ int layernorm_rows_ex(const float* x, const float* g, const float* bta, float ep
     const bool lp16 = out_lp && lp_dtype == CPT_BF16;
 #define LNK(LPT, GI)                                                                                                                              \
     do {                                                                                                                                          \
-        if (rpw == 2) layernorm_rows_kernel<LPT, GI, 2><<<grid, block, 0, s>>>(x, g, bta, eps, out_f32, (LPT*)out_lp, R, H, grp, grp_stride, grp_off, resid, dr, pre_out, (signed char*)out_lo, x_parts, x_stride, out_panel, stat_out, drows, keep_out, resid_stat, resid_g, resid_b, odr); \
-        else if (H == 768) layernorm_rows_kernel<LPT, GI, 1, 3><<<grid, block, 0, s>>>(x, g, bta, eps, out_f32, (LPT*)out_lp, R, H, grp, grp_stride, grp_off, resid, dr, pre_out, (signed char*)out_lo, x_parts, x_stride, out_panel, stat_out, drows, keep_out, resid_stat, resid_g, resid_b, odr); \
-        else layernorm_rows_kernel<LPT, GI, 1><<<grid, block, 0, s>>>(x, g, bta, eps, out_f32, (LPT*)out_lp, R, H, grp, grp_stride, grp_off, resid, dr, pre_out, (signed char*)out_lo, x_parts, x_stride, out_panel, stat_out, drows, keep_out, resid_stat, resid_g, resid_b, odr);          \
+        if (rpw == 2) layernorm_rows_kernel<LPT, GI, 2><<<grid, block, 0, s>>>(x, g, bta, eps, out_f32, (LPT*)out_lp, R, H, grp, grp_stride, grp_off, e.resid, dr, e.pre_out, (signed char*)e.out_lo, e.x_parts, e.x_stride, e.out_panel, e.stat_out, drows, keep_out, e.resid_stat, e.resid_g, e.resid_b, odr); \
+        else if (H == 768) layernorm_rows_kernel<LPT, GI, 1, 3><<<grid, block, 0, s>>>(x, g, bta, eps, out_f32, (LPT*)out_lp, R, H, grp, grp_stride, grp_off, e.resid, dr, e.pre_out, (signed char*)e.out_lo, e.x_parts, e.x_stride, e.out_panel, e.stat_out, drows, keep_out, e.resid_stat, e.resid_g, e.resid_b, odr); \
+        else layernorm_rows_kernel<LPT, GI, 1><<<grid, block, 0, s>>>(x, g, bta, eps, out_f32, (LPT*)out_lp, R, H, grp, grp_stride, grp_off, e.resid, dr, e.pre_out, (signed char*)e.out_lo, e.x_parts, e.x_stride, e.out_panel, e.stat_out, drows, keep_out, e.resid_stat, e.resid_g, e.resid_b, odr);          \
     } while (0)
     if (lp16) { if (gelu_in) LNK(bf16, true); else LNK(bf16, false); }
     else      { if (gelu_in) LNK(float, true); else LNK(float, false); }

@@ -312,10 +312,12 @@ int cpt_train_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* o, 
 /* backward of loss = loss_scale * mean over labelled rows; uses the workspace cpt_train_fwd filled.
  * WRITE / ACCUMULATE contract of g's tensors (ABI 5):
  *   WRITTEN whole by every call (previous contents ignored, never added to): every Linear weight gradient -- w_qkv, w_ao, w_in, w_out of each
- *     layer, w_img, w_pool, w_tr, w_rel -- and, with the MLM head, the tied word-embedding / decoder table (decoder gradient written, lookup
+ *     layer, w_img and the weights of the model's head (w_tr, or w_pool and w_rel) -- and, with the MLM head, the tied word-embedding / decoder table (decoder gradient written, lookup
  *     gradients added behind it);
  *   ACCUMULATED into with atomics (must hold zeros, or whatever the caller wants added to): every bias and LayerNorm gain / shift vector, the
  *     position and token-type tables, and the word table when the model has no MLM head.
+ *   LEFT UNTOUCHED: with the MLM head, w_pool and w_rel -- the pooler and the relation head take no part in that loss, so neither cpt_train_bwd
+ *     nor cpt_train_zero_grads writes these two tensors; a caller that reads them must clear them itself.
  * cpt_train_zero_grads clears exactly the second group.  A caller that accumulates micro-batches must therefore ADD the written tensors
  * itself between calls (cpt_amd/train.py keeps a copy and adds it); skipping the zero launch sums the vectors but OVERWRITES the matrices. */
 int cpt_train_bwd(const cpt_model* m, const cpt_batch* b, const cpt_model_grads* g, float loss_scale,
