@@ -92,6 +92,10 @@ _SIGS = {
     "cpt_rel2_workspace_bytes": (C.c_size_t, [C.c_int]),
     "cpt_rel2_scores": (C.c_int, [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "cpt_vcr_qar_choose": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "cpt_gqa_choose": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]),
+    "cpt_nsp_choose": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "cpt_grad_clip_workspace_bytes": (C.c_size_t, []),
+    "cpt_grad_clip": (C.c_int, [vp, C.c_size_t, C.c_float, vp, vp, vp, C.c_size_t, vp]),
     "cpt_train_fwd_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(Batch), C.POINTER(Outputs), vp, C.c_size_t, vp, BUCKET_CB, vp,
                                      C.POINTER(Dropout)]),
     "cpt_train_bwd_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(Batch), C.POINTER(ModelGrads), C.c_float, vp, vp, C.c_size_t, vp,

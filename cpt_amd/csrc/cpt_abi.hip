@@ -1058,3 +1058,34 @@ int cpt_vcr_qar_choose(const float* q_a, const float* qa_r, int n_q, int n_ans, 
 }
 
 }  // extern "C"
+
+// ---- GQA / VCR Q->A evaluation choices and global-norm clipping (choose.hip) ----
+extern "C" {
+
+int cpt_gqa_choose(const float* scores, int R, int C, const int32_t* piece_sid, const int32_t* gt_sid, int G, int64_t* pred, uint8_t* correct,
+                   int32_t* counts, void* stream) {
+    if (!scores || !piece_sid || !gt_sid || !pred || !correct) return abi_fail(CPT_ERR_NULL, "cpt_gqa_choose: null argument");
+    if (R <= 0 || C <= 0 || G <= 0) return abi_fail(CPT_ERR_SHAPE, "cpt_gqa_choose: R %d C %d G %d", R, C, G);
+    return abi_check(cpt::gqa_choose(scores, R, C, piece_sid, gt_sid, G, pred, correct, counts, (hipStream_t)stream), "cpt_gqa_choose");
+}
+
+int cpt_nsp_choose(const float* rel, int N, int n_rel, int interval, const int64_t* labels, float* scores, int64_t* pred, uint8_t* correct,
+                   int32_t* counts, void* stream) {
+    if (!rel || !labels || !scores || !pred || !correct) return abi_fail(CPT_ERR_NULL, "cpt_nsp_choose: null argument");
+    if (N <= 0 || n_rel < 2 || interval <= 0) return abi_fail(CPT_ERR_SHAPE, "cpt_nsp_choose: N %d n_rel %d (>= 2) interval %d", N, n_rel, interval);
+    if (N % interval) return abi_fail(CPT_ERR_SHAPE, "cpt_nsp_choose: %d sequences are no whole number of questions of %d choices", N, interval);
+    return abi_check(cpt::nsp_choose(rel, N / interval, interval, n_rel, labels, scores, pred, correct, counts, (hipStream_t)stream), "cpt_nsp_choose");
+}
+
+size_t cpt_grad_clip_workspace_bytes(void) { return cpt::grad_clip_ws_bytes(); }
+
+int cpt_grad_clip(float* g, size_t n, float max_norm, const double* sq_in, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!g || !out || !workspace) return abi_fail(CPT_ERR_NULL, "cpt_grad_clip: null argument");
+    if (n == 0) return abi_fail(CPT_ERR_SHAPE, "cpt_grad_clip: empty buffer");
+    if (((uintptr_t)g & 3) || ((uintptr_t)workspace & 3)) return abi_fail(CPT_ERR_SHAPE, "cpt_grad_clip: g and workspace must be 4-byte aligned");
+    if (workspace_bytes < cpt::grad_clip_ws_bytes())
+        return abi_fail(CPT_ERR_WORKSPACE, "cpt_grad_clip: workspace %zu < %zu bytes", workspace_bytes, cpt::grad_clip_ws_bytes());
+    return abi_check(cpt::grad_clip(g, n, max_norm, sq_in, out, workspace, (hipStream_t)stream), "cpt_grad_clip");
+}
+
+}  // extern "C"

@@ -297,5 +297,12 @@ int rel2_bwd(int lp, const float* pooled, int B, int H, int n_rel, int B0, const
 int rel2_check_labels(const int64_t* labels, const int64_t* labels_host, int B, int n_rel, const char* who, hipStream_t s);   // host: [-1, n_rel)
 int qar_choose(const float* q_a, const float* qa_r, int n_q, int n_ans, int n_rats, const int64_t* ans_label, const int64_t* rat_label,
                int64_t* preds, uint8_t* flags, int* counts, hipStream_t s);
+// choose.hip: GQA / VCR Q->A evaluation choices and global-norm clipping (cpt_gqa_choose, cpt_nsp_choose, cpt_grad_clip)
+int gqa_choose(const float* scores, int R, int C, const int32_t* piece_sid, const int32_t* gt_sid, int G, int64_t* pred, uint8_t* correct, int* counts,
+               hipStream_t s);
+int nsp_choose(const float* rel, int n_q, int interval, int n_rel, const int64_t* labels, float* scores, int64_t* pred, uint8_t* correct, int* counts,
+               hipStream_t s);
+size_t grad_clip_ws_bytes();
+int grad_clip(float* g, size_t n, float max_norm, const double* sq_in, float* out, void* ws, hipStream_t s);
 
 }  // namespace cpt

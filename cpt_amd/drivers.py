@@ -292,3 +292,213 @@ def train_vcr_qar_batch(model, optimizer, scheduler, batches, opts, device, glob
             model.zero_grad()
             global_step += 1
     return global_step, losses
+
+
+# ---- GQA-CPT (Oscar/oscar/fewshot/gqa_cpt.py; BASELINE config 4) and VCR Q->A (fewshot/vcr_nsp_cpt.py; config 5) -----------------------------
+def _seq_feats(f, n, device):
+    """img_feats (Li, D) of one question expanded to its n sequences on the device (the collate functions stack it per sequence)."""
+    f = torch.as_tensor(f).to(device, non_blocking=True)
+    return f.unsqueeze(0).expand(n, -1, -1) if f.dim() == 2 else f
+
+
+def val_gqa(model, questions, labels, tokenizer, device, batch_questions=256):
+    """Evaluation pass of gqa_cpt.py:558-636 (evaluate) on REC_MLM_CPT.  questions: prompts.assemble_gqa dicts with ``img_feats`` (Li, D) and
+    ``igt``, the question's ground-truth label indices (eval_dic[str(q_id)]); labels: the data set's answer strings.  Questions are sharded over
+    ranks; per batch ONE forward scores the label columns only (vocab_columns = every label's first word-piece id, duplicates kept) at the first
+    [MASK] slot, and the argmax, the multi-ground-truth correctness and their count run in one launch (cpt_gqa_choose); the fixed-shape
+    predictions, flags and (n, C) logits are gathered to every rank.  Accuracy as the reference: results de-duplicated by question_id (last
+    wins), divided by the number of questions.  Returns {"preds" (n,) label columns, "answers" [the first-piece strings the reference reports],
+    "correct" (n,) uint8, "logits" (n, C), "q_ids", "acc"}."""
+    model.eval()
+    token_ids, label_sid, piece_sid = scoring.gqa_string_ids(labels, tokenizer)
+    _, answer_labels = scoring.gqa_first_pieces(labels, tokenizer)
+    C = len(labels)
+    cols = torch.tensor(token_ids, dtype=torch.int64, device=device)
+    piece = torch.tensor(piece_sid, dtype=torch.int32, device=device)
+    gt_all = scoring.gqa_gt_table([q["igt"] for q in questions], label_sid)
+    rank, world = cdist.rank_world()
+    lo, hi = cdist.shard_range(len(questions), rank, world)
+    preds = torch.full((hi - lo,), -1, dtype=torch.int64, device=device)
+    correct = torch.zeros((hi - lo,), dtype=torch.uint8, device=device)
+    logits = torch.zeros((hi - lo, C), dtype=torch.float32, device=device)
+    t = lambda x: torch.as_tensor(x)
+    for start in range(lo, hi, batch_questions):
+        chunk = questions[start:min(start + batch_questions, hi)]
+        ids = torch.stack([t(q["input_ids"]) for q in chunk]).to(device, non_blocking=True)
+        seg = torch.stack([t(q["segment_ids"]) for q in chunk]).to(device, non_blocking=True)
+        msk = torch.stack([t(q["input_mask"]) for q in chunk]).to(device, non_blocking=True)
+        feats = torch.stack([t(q["img_feats"]) for q in chunk]).to(device, non_blocking=True).float()
+        mpos = torch.tensor([int(q["mask_token_pos"][0]) for q in chunk], dtype=torch.int64).to(device, non_blocking=True)   # raw_batch[-1][0]
+        with torch.no_grad():
+            sc = model(ids, seg, msk, img_feats=feats, mask_token_pos=mpos, vocab_columns=cols)[0]
+        p, c = scoring.gqa_choose_device(sc, piece, gt_all[start:start + len(chunk)])
+        i = start - lo
+        preds[i:i + len(chunk)], correct[i:i + len(chunk)], logits[i:i + len(chunk)] = p, c, sc
+    n = len(questions)
+    preds = cdist.gather_fixed(preds, n, fill=-1).cpu()
+    correct = cdist.gather_fixed(correct, n, fill=0).cpu()
+    logits = cdist.gather_fixed(logits, n, fill=0).cpu()
+    q_ids = [int(t(q["q_id"]).reshape(-1)[0]) for q in questions]
+    last = {}
+    for i, qid in enumerate(q_ids):        # results_dic = {k["question_id"]: k ...}: the last entry wins (gqa_cpt.py:619)
+        last[qid] = i
+    acc = float(correct[sorted(last.values())].sum().item()) / n
+    return {"preds": preds, "answers": [answer_labels[int(p)] for p in preds.tolist()], "correct": correct, "logits": logits, "q_ids": q_ids,
+            "acc": acc}
+
+
+def gqa_label_grid(input_ids, attention_mask, label_id, label_token_ids):
+    """gqa_cpt.py:428-435: a grid of -1 shaped like attention_mask (B, Lt + Li) with label_token_ids[label] at EVERY input_ids == 103 slot
+    ([MASK]); label_id (B,) or (B, 1) the first ground-truth label of each question.  The slots are taken in row-major order and the labels in
+    batch order, as the reference's index assignment pairs them: a batch whose sequences do not hold exactly one [MASK] each raises, as the
+    assignment does there."""
+    grid = torch.full(attention_mask.shape, -1, dtype=torch.long, device=input_ids.device)
+    want = label_token_ids.to(input_ids.device)[label_id.to(input_ids.device).long().reshape(-1)]
+    idx = (input_ids == 103).nonzero(as_tuple=False)
+    if idx.size(0) != want.numel():
+        raise RuntimeError("GQA label grid: %d [MASK] slots for %d labels" % (idx.size(0), want.numel()))
+    grid[idx[:, 0], idx[:, 1]] = want
+    return grid
+
+
+def gqa_accumulation(n_examples, per_gpu_train_batch_size, world_size, n_batches, num_train_epochs=1, max_steps=0):
+    """gqa_cpt.py:328-334: gradient_accumulation_steps = max(1, len(dataset) // (per_gpu_bs * world)) and t_total (max_steps, else
+    len(dataloader) // gradient_accumulation_steps * num_train_epochs).  Returns (gradient_accumulation_steps, t_total)."""
+    gas = max(n_examples // (per_gpu_train_batch_size * world_size), 1)
+    t_total = max_steps if max_steps > 0 else n_batches // gas * num_train_epochs
+    return gas, t_total
+
+
+def set_dropout(model, p):
+    """The adjust_dp switch of gqa_cpt.py:403-412 (0.3 from epoch 3 on): the reference sets ``p`` of model.dropout, model.bert.dropout and
+    model.bert.embeddings.dropout.  Here the training step draws its masks from config.hidden_dropout_prob (train.dropout_for), one rate for
+    every hidden dropout of the step, so that is set too: the next training forward's cpt_dropout carries it."""
+    model.config.hidden_dropout_prob = float(p)
+    for owner in (model, getattr(model, "bert", None), getattr(getattr(model, "bert", None), "embeddings", None)):
+        d = getattr(owner, "dropout", None)
+        if isinstance(d, torch.nn.Dropout):
+            d.p = float(p)
+
+
+def _accumulate(model, optimizer, scheduler, micro_losses, opts, global_step, use_device_clip=None):
+    """The accumulation loop both drivers share (gqa_cpt.py:445-462, vcr_nsp_cpt.py:452-473).  micro_losses yields one loss per micro-step; it is
+    divided by gradient_accumulation_steps when that is > 1, backward and the global-norm clip run on EVERY micro-step (in place on the
+    accumulated gradient), and every gradient_accumulation_steps micro-steps scheduler.step() runs BEFORE optimizer.step(), then
+    model.zero_grad().  The clip is optimizer.clip_grad_norm_device (no host synchronisation) when the optimizer has it -- use_device_clip=False
+    forces torch.nn.utils.clip_grad_norm_.  Returns (global_step, [loss tensors, as divided], [gradient norms before each clip])."""
+    gas = max(1, int(getattr(opts, "gradient_accumulation_steps", 1)))
+    max_norm = float(getattr(opts, "max_grad_norm", 1.0))
+    if use_device_clip is None:
+        use_device_clip = hasattr(optimizer, "clip_grad_norm_device")
+    losses, norms = [], []
+    for step, loss in enumerate(micro_losses):
+        if gas > 1:
+            loss = loss / gas
+        loss.backward()
+        if use_device_clip:
+            norms.append(optimizer.clip_grad_norm_device(max_norm))
+        else:
+            norms.append(torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm))
+        losses.append(loss.detach())
+        if (step + 1) % gas == 0:
+            scheduler.step()
+            optimizer.step()
+            model.zero_grad()
+            global_step += 1
+    return global_step, losses, norms
+
+
+def train_gqa_batch(model, optimizer, scheduler, batches, opts, device, label_token_ids, global_step=0, use_device_clip=None):
+    """One epoch of gqa_cpt.py:423-462 over ``batches``: dicts with input_ids (B, Lt), attention_mask (B, Lt + Li), segment_ids, img_feats
+    (B, Li, D) and label_id (B,) or (B, 1).  Label grid of gqa_label_grid, loss / gradient_accumulation_steps, backward and clip on every
+    micro-step, scheduler before optimizer, model.zero_grad() after (_accumulate).  use_device_clip: None = optimizer.clip_grad_norm_device when
+    the optimizer has it, False = torch.nn.utils.clip_grad_norm_.  Returns (global_step, [loss tensors, as divided])."""
+    global_step, losses, _ = _gqa_pass(model, optimizer, scheduler, batches, opts, device, label_token_ids, global_step, use_device_clip)
+    return global_step, losses
+
+
+def _gqa_pass(model, optimizer, scheduler, batches, opts, device, label_token_ids, global_step, use_device_clip):
+    model.train()
+    label_token_ids = torch.as_tensor(label_token_ids, dtype=torch.long).to(device)
+
+    def micro():
+        for host_batch in batches:
+            b = {k: torch.as_tensor(v).to(device) for k, v in host_batch.items()}
+            grid = gqa_label_grid(b["input_ids"], b["attention_mask"], b["label_id"], label_token_ids)
+            yield model(b["input_ids"], b["segment_ids"], b["attention_mask"], img_feats=b["img_feats"].float(), masked_lm_labels=grid)[0]
+    return _accumulate(model, optimizer, scheduler, micro(), opts, global_step, use_device_clip)
+
+
+def _vcr_block(chunk, device):
+    """Questions (prompts.assemble_vcr dicts + ``img_feats`` (Li, D)) concatenated in vcr_collate_fn's layout: one row per answer choice."""
+    t = lambda x: torch.as_tensor(x)
+    interval = chunk[0]["input_ids"].shape[0]
+    if any(q["input_ids"].shape[0] != interval for q in chunk):
+        raise ValueError("VCR Q->A: every question of a pass needs the same number of answer choices")
+    return {"input_ids": torch.cat([t(q["input_ids"]) for q in chunk], 0).to(device, non_blocking=True),
+            "attention_mask": torch.cat([t(q["input_mask"]) for q in chunk], 0).to(device, non_blocking=True),
+            "token_type_ids": torch.cat([t(q["segment_ids"]) for q in chunk], 0).to(device, non_blocking=True),
+            "img_feats": torch.cat([_seq_feats(q["img_feats"], interval, device) for q in chunk], 0).float().contiguous()}, interval
+
+
+def _vcr_label(q):
+    lb = q["label"]
+    return int(lb[0] if isinstance(lb, (list, tuple)) else lb)
+
+
+def val_vcr(model, questions, device, batch_questions=8):
+    """Evaluation pass of vcr_nsp_cpt.py:583-620 (evaluate) on NSPCPT.  questions: prompts.assemble_vcr dicts with ``img_feats`` (Li, D).
+    Questions are sharded over ranks (whole questions per rank); per batch one forward gives the relation scores and ONE launch
+    (cpt_nsp_choose) the choice scores 1 - softmax(rel)[:, 1], each question's argmax and its correctness; the fixed-shape predictions, flags
+    and (n_q, interval) choice scores are gathered to every rank.  Accuracy as the reference: results de-duplicated by questionId (last wins),
+    divided by the number of questions.  Returns {"preds" (n_q,), "correct" (n_q,) uint8, "scores" (n_q, interval), "q_ids", "acc"}."""
+    model.eval()
+    interval = questions[0]["input_ids"].shape[0]
+    rank, world = cdist.rank_world()
+    lo, hi = cdist.shard_range(len(questions), rank, world)
+    preds = torch.full((hi - lo,), -1, dtype=torch.int64, device=device)
+    correct = torch.zeros((hi - lo,), dtype=torch.uint8, device=device)
+    scores = torch.zeros((hi - lo, interval), dtype=torch.float32, device=device)
+    for start in range(lo, hi, batch_questions):
+        chunk = questions[start:min(start + batch_questions, hi)]
+        b, iv = _vcr_block(chunk, device)
+        if iv != interval:
+            raise ValueError("VCR Q->A: every question of a pass needs the same number of answer choices")
+        with torch.no_grad():
+            rel = model(b["input_ids"], b["token_type_ids"], b["attention_mask"], img_feats=b["img_feats"])[0]
+        sc, p, c = scoring.nsp_choose_device(rel, interval, [_vcr_label(q) for q in chunk])
+        i, nq = start - lo, len(chunk)
+        preds[i:i + nq], correct[i:i + nq], scores[i:i + nq] = p, c, sc.view(nq, interval)
+    n = len(questions)
+    preds = cdist.gather_fixed(preds, n, fill=-1).cpu()
+    correct = cdist.gather_fixed(correct, n, fill=0).cpu()
+    scores = cdist.gather_fixed(scores, n, fill=0).cpu()
+    q_ids = [int(q["q_id"]) for q in questions]
+    last = {}
+    for i, qid in enumerate(q_ids):        # results_dic = {k["questionId"]: k ...}: the last entry wins (vcr_nsp_cpt.py:619)
+        last[qid] = i
+    acc = float(correct[sorted(last.values())].sum().item()) / n
+    return {"preds": preds, "correct": correct, "scores": scores, "q_ids": q_ids, "acc": acc}
+
+
+def train_vcr_batch(model, optimizer, scheduler, batches, opts, device, global_step=0, use_device_clip=None):
+    """One epoch of vcr_nsp_cpt.py:430-473 over ``batches`` (lists of prompts.assemble_vcr dicts with img_feats, one list per micro-step, one
+    ``interval`` per pass): class 0 at each question's correct choice and 1 elsewhere (scoring.nsp_choice_labels), the NSP loss, and the
+    accumulation loop of train_gqa_batch (_accumulate).  Returns (global_step, [loss tensors, as divided])."""
+    global_step, losses, _ = _vcr_pass(model, optimizer, scheduler, batches, opts, device, global_step, use_device_clip)
+    return global_step, losses
+
+
+def _vcr_pass(model, optimizer, scheduler, batches, opts, device, global_step, use_device_clip):
+    model.train()
+    batches = list(batches)
+    interval = batches[0][0]["input_ids"].shape[0] if batches else 0
+
+    def micro():
+        for chunk in batches:
+            b, iv = _vcr_block(chunk, device)
+            if iv != interval:
+                raise ValueError("VCR Q->A: one interval per pass (got %d after %d)" % (iv, interval))
+            cls_labels = scoring.nsp_choice_labels([_vcr_label(q) for q in chunk], interval, len(chunk) * interval, device)
+            yield model(b["input_ids"], b["token_type_ids"], b["attention_mask"], next_sentence_label=cls_labels, img_feats=b["img_feats"])[0]
+    return _accumulate(model, optimizer, scheduler, micro(), opts, global_step, use_device_clip)

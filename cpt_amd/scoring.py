@@ -454,3 +454,110 @@ def vcr_qar_accuracy(results, n_examples):
     """vcr_qar_nsp_cpt.py:682-685: results de-duplicated by questionId (a dict: the LAST entry wins), acc = correct / len(eval_dataset)."""
     dic = {r["questionId"]: r for r in results}
     return sum([x["correct"] for x in dic.values()]) / n_examples
+
+
+# ---- GQA-CPT (Oscar/oscar/fewshot/gqa_cpt.py evaluate(), :558-636) ------------------------------------------------------------------------
+def gqa_first_pieces(labels, tokenizer):
+    """gqa_cpt.py:566-568: per answer label its first word-piece -- (label_token_ids [its vocabulary id], answer_labels [the piece as a string])."""
+    pieces = [tokenizer.tokenize(lb) for lb in labels]
+    return [tokenizer.convert_tokens_to_ids(p)[0] for p in pieces], [p[0] for p in pieces]
+
+
+def gqa_string_ids(labels, tokenizer):
+    """The strings evaluate() compares (gqa_cpt.py:604-611) as integer ids, quirk kept: the PREDICTED string is the first word-piece of the chosen
+    label (answer_labels[p]), the ground-truth strings are the WHOLE labels (labels[x]).  Returns (label_token_ids, label_sid, piece_sid), lists
+    of len(labels): label_token_ids as gqa_first_pieces; label_sid[i] = one id per distinct label string (the index of its first occurrence);
+    piece_sid[i] = the id of the label string equal to label i's first piece, -2 when no label is that string (the prediction is then never
+    right)."""
+    token_ids, answer_labels = gqa_first_pieces(labels, tokenizer)
+    sid = {}
+    for i, lb in enumerate(labels):
+        sid.setdefault(lb, i)
+    return token_ids, [sid[lb] for lb in labels], [sid.get(p, -2) for p in answer_labels]
+
+
+def gqa_choose_reference(logits, labels, answer_labels, igts, q_ids=None):
+    """Host restatement of evaluate()'s per-batch loop (gqa_cpt.py:600-612), no device call: logits (R, C) the label-order columns of the [MASK]
+    rows, answer_labels the first-piece strings, igts per question its ground-truth label indices (eval_dic[str(qid)]).  Returns the result dicts
+    the reference pickles: answer, question_id, gt, igt, correct, logits."""
+    preds = logits.argmax(1)
+    preds = [answer_labels[int(p)] for p in preds]
+    out = []
+    for i, (p, igt) in enumerate(zip(preds, igts)):
+        gt = [labels[int(x)] for x in igt]
+        correct = [x == p for x in gt]
+        correct = max(correct)
+        out.append({"answer": p, "question_id": int(q_ids[i]) if q_ids is not None else i, "gt": gt, "igt": list(igt), "correct": correct,
+                    "logits": logits[i].cpu().numpy()})
+    return out
+
+
+def gqa_accuracy(results, n_examples):
+    """gqa_cpt.py:619-620: results de-duplicated by question_id (a dict: the LAST entry wins), acc = correct / len(eval_dataset)."""
+    dic = {r["question_id"]: r for r in results}
+    return sum([x["correct"] for x in dic.values()]) / n_examples
+
+
+def gqa_gt_table(igts, label_sid):
+    """(R, G) int32 string ids of every question's ground-truth labels, padded with -1 (G = the longest list, at least 1)."""
+    G = max(1, max((len(x) for x in igts), default=1))
+    t = torch.full((len(igts), G), -1, dtype=torch.int32)
+    for i, x in enumerate(igts):
+        if len(x):
+            t[i, :len(x)] = torch.tensor([label_sid[int(j)] for j in x], dtype=torch.int32)
+    return t
+
+
+def gqa_choose_device(scores, piece_sid, gt_sid, counts=None):
+    """The same choice on the device, one launch (cpt_gqa_choose): scores (R, C) fp32 on the GPU, piece_sid (C,) and gt_sid (R, G) int32 (moved
+    to the device when they are not there).  Returns (pred (R,) int64 = the argmax column, correct (R,) uint8); ``counts`` (1,) int32 device
+    tensor, optional: += the number of correct rows."""
+    from . import _lib as L
+    if not scores.is_cuda:
+        raise RuntimeError("cpt_amd: gqa_choose_device needs the logits on the GPU (no CPU fallback: gqa_choose_reference is the host form)")
+    dev = scores.device
+    sc = scores.contiguous().float()
+    R, C = sc.shape
+    ps = torch.as_tensor(piece_sid, dtype=torch.int32).to(dev).contiguous()
+    gt = torch.as_tensor(gt_sid, dtype=torch.int32).to(dev).contiguous()
+    if ps.numel() != C or gt.dim() != 2 or gt.size(0) != R:
+        raise ValueError("gqa_choose_device: scores %s, piece_sid %s, gt_sid %s" % (tuple(sc.shape), tuple(ps.shape), tuple(gt.shape)))
+    if counts is not None and (counts.dtype != torch.int32 or counts.numel() != 1 or not counts.is_cuda):
+        raise ValueError("gqa_choose_device: counts must be a (1,) int32 device tensor")
+    pred = torch.empty(R, dtype=torch.int64, device=dev)
+    correct = torch.empty(R, dtype=torch.uint8, device=dev)
+    L.check(L.lib().cpt_gqa_choose(sc.data_ptr(), R, C, ps.data_ptr(), gt.data_ptr(), gt.size(1), pred.data_ptr(), correct.data_ptr(), L.ptr(counts),
+                                   L.stream_ptr()), "cpt_gqa_choose")
+    return pred, correct
+
+
+# ---- VCR Q->A (Oscar/oscar/fewshot/vcr_nsp_cpt.py evaluate(), :583-620) ---------------------------------------------------------------------
+def nsp_choose_device(rel, interval, labels, counts=None):
+    """nsp_choose on the device, one launch (cpt_nsp_choose): rel (N, n_rel) fp32 relation scores on the GPU, labels (N / interval,) the
+    questions' answer labels.  Returns (scores (N,) = 1 - softmax(rel)[:, 1], preds (n_q,) int64, flags (n_q,) uint8 = pred == label);
+    ``counts`` (1,) int32 device tensor, optional: += the number of correct questions.  N % interval != 0 raises (CPT_ERR_SHAPE)."""
+    from . import _lib as L
+    if not rel.is_cuda:
+        raise RuntimeError("cpt_amd: nsp_choose_device needs the relation scores on the GPU (no CPU fallback: nsp_choose is the host form)")
+    dev = rel.device
+    x = rel.contiguous().float()
+    N, n_rel = x.shape
+    interval = int(interval)
+    n_q = N // interval if interval > 0 else 0
+    lb = torch.as_tensor(labels, dtype=torch.int64).to(dev).contiguous()
+    if interval > 0 and N % interval == 0 and lb.numel() != n_q:
+        raise ValueError("nsp_choose_device: %d labels for %d questions" % (lb.numel(), n_q))
+    if counts is not None and (counts.dtype != torch.int32 or counts.numel() != 1 or not counts.is_cuda):
+        raise ValueError("nsp_choose_device: counts must be a (1,) int32 device tensor")
+    scores = torch.empty(N, dtype=torch.float32, device=dev)
+    preds = torch.empty(n_q, dtype=torch.int64, device=dev)
+    flags = torch.empty(n_q, dtype=torch.uint8, device=dev)
+    L.check(L.lib().cpt_nsp_choose(x.data_ptr(), N, n_rel, interval, lb.data_ptr(), scores.data_ptr(), preds.data_ptr(), flags.data_ptr(),
+                                   L.ptr(counts), L.stream_ptr()), "cpt_nsp_choose")
+    return scores, preds, flags
+
+
+def nsp_accuracy(results, n_examples):
+    """vcr_nsp_cpt.py:619-620: results de-duplicated by questionId (the LAST entry wins), acc = correct / len(eval_dataset)."""
+    dic = {r["questionId"]: r for r in results}
+    return sum([x["correct"] for x in dic.values()]) / n_examples

@@ -477,6 +477,51 @@ class FusedAdamW(object):
         self._clip = min(1.0, max_norm / (norm + 1e-6))
         return norm
 
+    def clip_grad_norm_device(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) on the device (cpt_grad_clip: two launches, a fixed-order sum), without
+        a host synchronisation.  Returns the norm before clipping as a device scalar; ``last_clip`` keeps the (2,) device tensor {norm, coef}.
+          * world size 1, or ``defer_reduce``: the flat gradient the ``p.grad`` views alias is scaled IN PLACE, so it may be called on every
+            micro-step of an accumulation window, as the GQA / VCR drivers do (gqa_cpt.py:454, vcr_nsp_cpt.py:461).  Parameters outside the
+            loss's graph (NO_GRAD_PREFIXES) add nothing to the norm: their ranges of the buffer are allocated zero and no backward holds a
+            pointer into them (_TrainState.ensure).
+          * data parallel without ``defer_reduce``: the AVERAGED gradient exists only as shards.  After the reduce-scatter the shards' squares
+            are summed on the device, all-reduced and divided by world**2, and this rank's shard is scaled in place.  Once per optimizer step,
+            behind the backward that closes the accumulation window: inside ``no_sync()`` or a second time it raises RuntimeError."""
+        self._ensure()
+        st = _state(self.eng)
+        if st.grad is None:
+            raise RuntimeError("cpt_amd: clip_grad_norm_device() before any backward")
+        dev = st.grad.device
+        if getattr(self, "_clip_ws", None) is None or self._clip_ws.device != dev:
+            self._clip_ws = torch.zeros(int(L.lib().cpt_grad_clip_workspace_bytes()), dtype=torch.uint8, device=dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        sharded = self.sync is not None and not self.defer_reduce
+        if sharded:
+            import torch.distributed as dist
+            if st.defer:
+                raise RuntimeError("cpt_amd: clip_grad_norm_device() inside no_sync(): the data-parallel gradient is averaged when the "
+                                   "accumulation window closes; clip once, behind its last backward (or build the optimizer with "
+                                   "defer_reduce=True to clip local gradients on every micro-step)")
+            if getattr(self, "_clipped_at", None) == self.step_count:
+                raise RuntimeError("cpt_amd: clip_grad_norm_device() twice before one optimizer.step(): the averaged data-parallel gradient "
+                                   "is clipped once per step")
+            self.sync.finish_reduce(st.grad)
+            buf = self.sync.gshard
+            sq = (buf.double() ** 2).sum().reshape(1)
+            if self.sync.collectives:
+                dist.all_reduce(sq)
+            sq = sq / float(self.world) ** 2
+            # (the shard holds the ranks' SUM; AdamW folds in 1 / world: scaling the sum by the mean's coefficient clips the mean)
+            L.check(L.lib().cpt_grad_clip(buf.data_ptr(), buf.numel(), float(max_norm), sq.data_ptr(), out.data_ptr(), self._clip_ws.data_ptr(),
+                                          self._clip_ws.numel(), L.stream_ptr()), "cpt_grad_clip")
+            self._clipped_at = self.step_count
+        else:
+            buf = st.grad
+            L.check(L.lib().cpt_grad_clip(buf.data_ptr(), buf.numel(), float(max_norm), None, out.data_ptr(), self._clip_ws.data_ptr(),
+                                          self._clip_ws.numel(), L.stream_ptr()), "cpt_grad_clip")
+        self.last_clip = out
+        return out[0]
+
     def _adamw(self, p_ptr, g_ptr, m_ptr, v_ptr, code_ptr, shadow_ptr, n, lr, wd, scale):
         if self.flags:
             L.check(L.lib().cpt_adamw_ex(p_ptr, g_ptr, m_ptr, v_ptr, code_ptr, shadow_ptr, n, lr, self.betas[0], self.betas[1], self.eps,

@@ -279,6 +279,33 @@ int cpt_vcr_qar_choose(const float* q_a, const float* qa_r, int n_q, int n_ans, 
                        int64_t* preds, uint8_t* flags, int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GQA-CPT and VCR Q->A evaluation choices, and global-norm gradient clipping, on the device.  Added beside ABI 8, no struct changed.
+ * torch.argmax rules throughout: the first maximum wins, NaN counts as the maximum (the first NaN wins), -0 == +0 is a tie.
+ * ---------------------------------------------------------------------------------------- */
+/* GQA answer choice of evaluate() (Oscar/oscar/fewshot/gqa_cpt.py:598-612) for R questions, one launch: scores [R][C] fp32 (device), the
+ * [MASK]-row logits of the C answer labels in label order.  pred [R] int64 = the argmax column.  Correctness runs on string ids: piece_sid [C]
+ * int32 = the id of the string the reference predicts for column c (the label's FIRST word-piece; -2 = equal to no label string), gt_sid [R][G]
+ * int32 = the ids of the question's ground-truth label strings, padded with -1.  correct [R] uint8 = any g: gt_sid[r][g] >= 0 and
+ * gt_sid[r][g] == piece_sid[pred[r]]; counts [1] int32 (optional) += the number of correct rows (device accumulation over batches). */
+int cpt_gqa_choose(const float* scores, int R, int C, const int32_t* piece_sid, const int32_t* gt_sid, int G, int64_t* pred, uint8_t* correct,
+                   int32_t* counts, void* stream);
+/* VCR Q->A choice of evaluate() (fewshot/vcr_nsp_cpt.py:600-611), one launch: rel [N][n_rel] fp32 relation scores (device, n_rel >= 2), N =
+ * n_q * interval sequences (CPT_ERR_SHAPE when interval does not divide N), labels [n_q] int64 (device).  scores [N] = 1 - softmax(rel[i])[1] in
+ * fp32 (NaN when the row holds one); pred [n_q] int64 = the argmax inside the question's interval; correct [n_q] uint8 = pred == label; counts
+ * [1] int32 (optional) += the number of correct questions. */
+int cpt_nsp_choose(const float* rel, int N, int n_rel, int interval, const int64_t* labels, float* scores, int64_t* pred, uint8_t* correct,
+                   int32_t* counts, void* stream);
+/* torch.nn.utils.clip_grad_norm_(max_norm, error_if_nonfinite=False) on one flat fp32 buffer g [n] (device), in place, two launches and no host
+ * synchronisation.  Launch 1 writes per-workgroup partial sums of squares; the last workgroup to finish adds them in index order (the same
+ * buffer gives the same norm bit for bit) and writes out [2] fp32 (device) = {norm, coef}, coef = min(1, max_norm / (norm + 1e-6)): a NaN norm
+ * gives a NaN coefficient, an infinite norm gives 0.  With sq_in (device double, optional) the norm is sqrt(*sq_in) -- a sum of squares formed
+ * elsewhere, e.g. all-reduced over the shards of a data-parallel gradient -- and g is only scaled.  Launch 2 multiplies g by coef (always, also
+ * when coef == 1, as torch does).  workspace: cpt_grad_clip_workspace_bytes() bytes (device); its first word is the finish ticket, which must
+ * hold 0 before the first call (a zeroed workspace) and is left 0 by every call. */
+size_t cpt_grad_clip_workspace_bytes(void);
+int cpt_grad_clip(float* g, size_t n, float max_norm, const double* sq_in, float* out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Few-shot training step (Oscar/oscar/fewshot/refcoco_cpt.py:231-249): forward that keeps the
  * activations, backward into caller-owned fp32 gradient tensors laid out like the parameters,
  * fused AdamW.  [MASK]-rows mode only (the loss of modeling_rec.py:147-150 sees only those rows).
