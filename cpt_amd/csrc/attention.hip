@@ -360,7 +360,7 @@ int attention(int dtype, const void* qkv, const int64_t* attn_mask, void* ctx, v
 //   softmax in fp32  (base 2, as the bf16 core), probabilities split in registers,
 //   O^T = V^T P^T    from V hi / lo tiles (row-major, transpose-read).
 // Output: ctx as fp32 [M][H], or (out_split) directly as the split copy [M][hi | hi | lo] (ld 3H) that the attention-output GEMM of the
-// mode reads -- the stand-alone cpt_split3 pass over ctx is gone.  2-D masks, L <= 224 (K + V hi / lo tiles: 112 KB at L = 224).
+// mode reads -- the stand-alone cpt_split3 pass over ctx is gone.  2-D masks, L <= 288 (K + V hi / lo tiles: 112 KB at NKB = 7, L <= 224; 148.6 KB at NKB = 9).
 __device__ __forceinline__ void split_chunk8(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {

@@ -891,6 +891,7 @@ int dropout_mask(int kind, unsigned char* out, int n0, int n1, int n2, const Dro
 // held in LDS but read from global memory (74 KB per head, L2-resident) and the query block shrinks to 16 rows -- 140 KB at
 // L = 288 with dropout instead of the 240 KB the QB = 32 / V-in-LDS form would need.
 constexpr int AB_QB = 32, AB_D = 64;
+constexpr int AB_ME_KEYS = 44 * 256 / AB_D;      // keys the largest QB = 32 instantiation (MAXE = 44) accumulates dK / dV for: 176
 template <typename T, int MAXE, int QB = AB_QB, bool VG = false>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const T* __restrict__ qkv, const int64_t* __restrict__ attn_mask,
                                                        const T* __restrict__ dctx, T* __restrict__ dqkv, int B, int L, int heads,
@@ -2083,7 +2084,7 @@ int attention_bwd_supported(int dtype, int L, int has_drop, int mask_3d) {
     if (!mask_3d && dtype == CPT_BF16 && g_attn_bwd_variant != 0 && L <= 288) return 1;
     if (dtype != CPT_BF16 && dtype != CPT_F32) return 0;
     const size_t lds = ((size_t)2 * L * 65 + 2 * AB_QB * 65 + (has_drop ? 3 : 2) * AB_QB * (L + 1) + L) * sizeof(float);
-    if (lds <= 160 * 1024) return 1;
+    if (lds <= 160 * 1024 && L <= AB_ME_KEYS) return 1;
     return L <= 288 && attn_bwd_vg_lds(L, has_drop) <= 160 * 1024;      // V from global memory, 16-query blocks
 }
 
@@ -2108,7 +2109,9 @@ int attention_bwd(int dtype, const void* qkv, const int64_t* attn_mask, const vo
         return attn_bwd_mfma_launch<9, true>(qkv, attn_mask, dctx, dqkv, B, L, heads, dr, s, dbias, ctx, stats);
     }
     size_t lds = ((size_t)2 * L * 65 + 2 * AB_QB * 65 + (dr.thresh ? 3 : 2) * AB_QB * (L + 1) + L) * sizeof(float);
-    const bool vg = lds > 160 * 1024;                      // beyond L ~ 176: the form that reads V from global memory (L <= 288)
+    // beyond L = 176 (with dropout: 161, where 160 KB of LDS end): the form that reads V from global memory (L <= 288).  The LDS bound alone let
+    // L = 177 .. 188 without dropout into the ME = 44 kernel, whose dK / dV accumulators end at key 176: rows 176 .. L - 1 of dK and dV were never written
+    const bool vg = lds > 160 * 1024 || L > AB_ME_KEYS;
     if (vg) {
         lds = attn_bwd_vg_lds(L, dr.thresh ? 1 : 0);
         if (L > 288 || lds > 160 * 1024) return CPT_ERR_SHAPE;

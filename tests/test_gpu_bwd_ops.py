@@ -88,6 +88,13 @@ def test_attention_bwd_against_oracle_autograd(dev, mode, L, p):
     assert _rel(db_d.cpu(), gb) < tol                     # the kernel's own bias-gradient sums
 
 
+def _guarded(rows, cols, dtype, dev, guard=64):
+    """[rows][cols] of `dtype` with `guard` rows of 0xFF bytes (NaN in fp32 and bf16) behind it -> (whole byte buffer, the tensor, bytes used)."""
+    item = torch.empty((), dtype=dtype).element_size()
+    buf = torch.full(((rows + guard) * cols * item,), 0xFF, dtype=torch.uint8, device=dev)
+    return buf, buf.view(dtype).view(rows + guard, cols)[:rows], rows * cols * item
+
+
 @pytest.mark.parametrize("p", [0.0, 0.1])
 @pytest.mark.parametrize("lp", ["bf16", "fp32"])
 @pytest.mark.parametrize("R", [480, 3840])
@@ -95,9 +102,25 @@ def test_layernorm_bwd_against_oracle_autograd(dev, R, lp, p):
     """y = layer_norm(dropout(o) + resid) as BertSelfOutput / BertOutput compute it: dx (= the residual's gradient), dgamma, dbeta, and -- with
     dropout -- the masked gradient of the dense output with its column sums, against autograd over oracle.layer_norm with the exported mask.
     With and without the two-stage column-sum scratch."""
+    _layernorm_bwd_case(dev, R, 768, lp, p)
+
+
+# R = 1 / 7: fewer rows than one workgroup takes; 2047 / 2049: each side of the switch from 4 to 8 rows per workgroup (ln_bwd_rpb_two_stage), both
+# with a ragged last workgroup.  H = 128 / 1024: the NA = 4 instantiation (H = 768 is NA = 3), one partly and one wholly filled lane array.
+_LN_EDGES = [(R, 768) for R in (1, 7, 2047, 2049)] + [(R, H) for H in (128, 1024) for R in (7, 2049)]
+
+
+@pytest.mark.parametrize("p", [0.0, 0.1])
+@pytest.mark.parametrize("lp", ["bf16", "fp32"])
+@pytest.mark.parametrize("R,H", _LN_EDGES)
+def test_layernorm_bwd_row_and_width_edges(dev, R, H, lp, p):
+    _layernorm_bwd_case(dev, R, H, lp, p)
+
+
+def _layernorm_bwd_case(dev, R, H, lp, p):
     from cpt_amd import _lib as Lb
-    H, step, site = 768, 5, 2 + 3 * 7
-    g = torch.Generator().manual_seed(R + int(p * 10))
+    step, site = 5, 2 + 3 * 7
+    g = torch.Generator().manual_seed(R + int(p * 10) + (0 if H == 768 else H))
     o = torch.randn(R, H, generator=g).requires_grad_(True)
     resid = (torch.randn(R, H, generator=g) * 1.5 + 0.2).requires_grad_(True)
     gam = (1 + 0.1 * torch.randn(H, generator=g)).requires_grad_(True)
@@ -113,8 +136,8 @@ def test_layernorm_bwd_against_oracle_autograd(dev, R, lp, p):
     lpt = torch.bfloat16 if lp == "bf16" else torch.float32
     dy_d, pre_d, gam_d = dy.to(dev), pre.detach().to(dev), gam.detach().to(dev)      # (held: a temporary's memory would be reused by the next copy)
     for scratch_on in (False, True):
-        dx = torch.empty(R, H, device=dev)
-        dxl = torch.empty(R, H, device=dev, dtype=lpt)
+        xbuf, dx, xused = _guarded(R, H, torch.float32, dev)
+        lbuf, dxl, lused = _guarded(R, H, lpt, dev)
         dg, db, dbias = (torch.zeros(H, device=dev) for _ in range(3))
         scratch = torch.empty(((R + 3) // 4) * 3 * H, device=dev) if scratch_on else None
         dr = Lb.Dropout(p_hidden=p, p_attn=p, seed=SEED, step=step)
@@ -122,6 +145,9 @@ def test_layernorm_bwd_against_oracle_autograd(dev, R, lp, p):
                                             Lb.CPT_BF16 if lp == "bf16" else Lb.CPT_F32, dg.data_ptr(), db.data_ptr(), R, H, C.byref(dr) if p > 0 else None, site,
                                             dbias.data_ptr(), scratch.data_ptr() if scratch_on else None, scratch.numel() * 4 if scratch_on else 0, Lb.stream_ptr()),
                  "cpt_layernorm_bwd")
+        torch.cuda.synchronize()
+        assert bool((xbuf[xused:] == 0xFF).all()) and bool((lbuf[lused:] == 0xFF).all())          # nothing written behind dx / dx_lp
+        assert torch.isfinite(dx).all() and torch.isfinite(dxl.float()).all()                     # and every row in front written
         assert _rel(dx.cpu(), resid.grad) < 2e-5
         assert _rel(dg.cpu(), gam.grad) < 1e-4 and _rel(db.cpu(), bet.grad) < 1e-4
         assert _rel(dxl.float().cpu(), o.grad) < (1e-2 if lp == "bf16" else 2e-5)
