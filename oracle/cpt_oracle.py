@@ -173,8 +173,7 @@ def bert_img_forward(sd, cfg, input_ids, token_type_ids=None, attention_mask=Non
     for i in range(cfg["num_hidden_layers"]):                                   # :100-126
         x = encoder_layer(sd, cfg, x, ext, i, prefix, drop)
         hiddens.append(x)
-    pooled = torch.tanh(F.linear(x[:, 0], sd[prefix + "pooler.dense.weight"],
-                                 sd[prefix + "pooler.dense.bias"]))             # :275
+    pooled = torch.tanh(_linear(x[:, 0], sd, prefix + "pooler.dense"))         # :275 (a GEMM like the others: bf16 operands under emulate_bf16)
     if all_hidden:
         return x, pooled, hiddens
     return x, pooled
@@ -217,11 +216,16 @@ def rec_mlm_cpt_forward(sd, cfg, input_ids, token_type_ids=None, attention_mask=
     return out
 
 
+def relation_head(sd, pooled, w_key="cls.seq_relationship.weight", b_key="cls.seq_relationship.bias"):
+    """The relation head on the pooled [CLS] (modeling_vcr.py:120-124): one GEMM, both operands through ``_lp``, the bias added wide."""
+    return F.linear(_lp(pooled), _lp(sd[w_key]), sd[b_key])
+
+
 def nsp_cpt_scores(sd, cfg, input_ids, token_type_ids, attention_mask, img_feats):
     """NSPCPT scoring head (Oscar/oscar/modeling/modeling_vcr.py:79-129): pooled
     [CLS] -> pretrained cls.seq_relationship Linear(H,3)."""
     _, pooled = bert_img_forward(sd, cfg, input_ids, token_type_ids, attention_mask, None, img_feats)
-    return F.linear(pooled, sd["cls.seq_relationship.weight"], sd["cls.seq_relationship.bias"])
+    return relation_head(sd, pooled)
 
 
 def nsp_cpt_forward(sd, cfg, input_ids, token_type_ids, attention_mask, img_feats, next_sentence_label=None,
@@ -229,7 +233,7 @@ def nsp_cpt_forward(sd, cfg, input_ids, token_type_ids, attention_mask, img_feat
     """NSPCPT.forward (Oscar/oscar/modeling/modeling_vcr.py:115-129): relation scores on the pooled [CLS]
     and, with labels, CrossEntropyLoss(ignore_index=-1) over the num_contrast_classes scores."""
     _, pooled = bert_img_forward(sd, cfg, input_ids, token_type_ids, attention_mask, None, img_feats)
-    rel = F.linear(pooled, sd[w_key], sd[b_key])
+    rel = relation_head(sd, pooled, w_key, b_key)
     if next_sentence_label is None:
         return (rel,)
     loss = F.cross_entropy(rel.view(-1, rel.size(-1)), next_sentence_label.view(-1), ignore_index=-1)
