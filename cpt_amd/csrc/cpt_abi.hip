@@ -1088,4 +1088,22 @@ int cpt_grad_clip(float* g, size_t n, float max_norm, const double* sq_in, float
     return abi_check(cpt::grad_clip(g, n, max_norm, sq_in, out, workspace, (hipStream_t)stream), "cpt_grad_clip");
 }
 
+int cpt_batch_extents(const int64_t* mask, int B, int Lt, int Li, const int64_t* mask_pos, int n_pos, int32_t* out, void* stream) {
+    if (!mask || !out || (n_pos > 0 && !mask_pos)) return abi_fail(CPT_ERR_NULL, "cpt_batch_extents: null argument");
+    if (B <= 0 || Lt <= 0 || Li < 0 || n_pos < 0) return abi_fail(CPT_ERR_SHAPE, "cpt_batch_extents: B %d Lt %d Li %d n_pos %d", B, Lt, Li, n_pos);
+    return abi_check(cpt::batch_extents(mask, B, Lt, Li, mask_pos, n_pos, out, (hipStream_t)stream), "cpt_batch_extents");
+}
+
+int cpt_trim_batch(const int64_t* input_ids, const int64_t* token_type, const int64_t* position_ids, const int64_t* attn_mask, const float* img_feats,
+                   int B, int Lt, int Li, int img_dim, int Lt_out, int Li_out, int64_t* input_ids_out, int64_t* token_type_out,
+                   int64_t* position_ids_out, int64_t* attn_mask_out, float* img_feats_out, void* stream) {
+    if (B <= 0 || Lt <= 0 || Li < 0 || Lt_out <= 0 || Lt_out > Lt || Li_out < 0 || Li_out > Li || (Li_out > 0 && img_dim <= 0))
+        return abi_fail(CPT_ERR_SHAPE, "cpt_trim_batch: B %d, %d + %d -> %d + %d, img_dim %d", B, Lt, Li, Lt_out, Li_out, img_dim);
+    if (!input_ids || !attn_mask || !input_ids_out || !attn_mask_out || (token_type && !token_type_out) || (position_ids && !position_ids_out) ||
+        (Li_out > 0 && (!img_feats || !img_feats_out)))
+        return abi_fail(CPT_ERR_NULL, "cpt_trim_batch: null argument");
+    return abi_check(cpt::trim_batch(input_ids, token_type, position_ids, attn_mask, img_feats, B, Lt, Li, img_dim, Lt_out, Li_out, input_ids_out,
+                                     token_type_out, position_ids_out, attn_mask_out, img_feats_out, (hipStream_t)stream), "cpt_trim_batch");
+}
+
 }  // extern "C"

@@ -11,8 +11,10 @@ tensors, in the layout ``test_collate`` (zeroshot/refcoco_cpt.py:159-172) produc
 """
 import logging
 
+import numpy as np
 import torch
 
+from . import batching
 from . import dist as cdist
 from . import scoring
 from .train import get_lr_sched
@@ -20,13 +22,44 @@ from .train import get_lr_sched
 logger = logging.getLogger(__name__)
 
 
-def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4, colour_columns_only=True):
+# ---- length-aware evaluation (batching.py): options of the val_* drivers, all off by default ----------------------------------------------------
+#   trim    the host arrays of every batch are cut to the part some sequence attends to BEFORE the H2D copy (batching.trim: no device copy, fewer
+#           PCIe bytes); the encoder then runs on (B, Lt' + Li').  Head-row outputs only, which is all these drivers read.
+#   bucket  each rank walks ITS shard by ascending length (batching.length_order; an item of several sequences -- a query, a VCR question, a VG
+#           pair -- stays whole and counts by its longest sequence) and writes every result back at the item's own index.
+def _item_length(mask, Lt):
+    """The length key of one item: text_len + regions of its longest sequence."""
+    t, r = batching.extents(mask, Lt)
+    return int((t + r).max())
+
+
+def _walk(n, size, keys=None):
+    """Lists of shard-local item indices, ``size`` per batch: in data set order, or (keys: bucket) by ascending length key, stable."""
+    order = list(range(n)) if keys is None else batching.length_order(keys, 0)[0].tolist()
+    return [order[i:i + size] for i in range(0, n, size)]
+
+
+def _sel(idx, device, bucket):
+    """Where the results of the items ``idx`` go in a shard-local result tensor: a slice in data set order, an index tensor under bucket."""
+    return torch.as_tensor(idx, device=device) if bucket else slice(idx[0], idx[-1] + 1)
+
+
+def _trim_host(b, head_pos=None):
+    """batching.trim of a host batch to its own batch extent -> (batch, Li')."""
+    lt, li = batching.batch_extent(b["attention_mask"], b["input_ids"].shape[1], head_pos)
+    return batching.trim(b, lt, li), li
+
+
+def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4, colour_columns_only=True, trim=False, bucket=False,
+                max_sequences=None):
     """queries: list of dicts with tensors ``img_feats (P,Li,D)``, ``input_ids (P,Lt)``,
     ``segment_ids``, ``attention_mask (P,Lt+Li)``, ``mask_token_pos (P,)`` and python lists
     ``colors`` (per proposal sequence: colour-token ids) and ``rects`` (per sequence: rectangles).
     Returns {global query index: (max_idx, rect)} on every rank.
     colour_columns_only (default): the decoder scores only the vocabulary columns the selection reads -- every colour id of the queries + ``none_id``
-    (zeroshot/refcoco_cpt.py:219 gathers exactly those out of the (P, V) scores) -- instead of all V; same chosen indices."""
+    (zeroshot/refcoco_cpt.py:219 gathers exactly those out of the (P, V) scores) -- instead of all V; same chosen indices.
+    trim / bucket: length-aware evaluation, see the top of this module.  max_sequences: batches are consecutive groups of whole queries with at
+    most that many proposal sequences (batching.pack_queries) instead of ``batch_queries`` queries each -- even launches for ragged queries."""
     model.eval()
     rank, world = cdist.rank_world()
     lo, hi = cdist.shard_range(len(queries), rank, world)
@@ -36,10 +69,19 @@ def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4
         col_ids = sorted({int(c) for q in queries for s in q["colors"] for c in s} | {int(none_id)})
         col_of = {c: i for i, c in enumerate(col_ids)}
         cols_dev = torch.tensor(col_ids, dtype=torch.int64, device=device)
-    for start in range(lo, hi, batch_queries):
-        chunk = queries[start:min(start + batch_queries, hi)]
-        cat = {k: torch.cat([q[k] for q in chunk], 0).to(device, non_blocking=True)
-               for k in ("img_feats", "input_ids", "segment_ids", "attention_mask", "mask_token_pos")}
+    order = list(range(hi - lo))
+    if bucket:
+        order = batching.length_order([_item_length(q["attention_mask"], q["input_ids"].shape[1]) for q in queries[lo:hi]], 0)[0].tolist()
+    if max_sequences is not None:
+        groups = [[order[i] for i in g] for g in batching.pack_queries([queries[lo + i]["input_ids"].size(0) for i in order], max_sequences)]
+    else:
+        groups = [order[i:i + batch_queries] for i in range(0, hi - lo, batch_queries)]
+    for idx_local in groups:
+        chunk = [queries[lo + i] for i in idx_local]
+        cat = {k: torch.cat([q[k] for q in chunk], 0) for k in ("img_feats", "input_ids", "segment_ids", "attention_mask", "mask_token_pos")}
+        if trim:
+            cat = _trim_host(cat, cat["mask_token_pos"])[0]
+        cat = {k: v.to(device, non_blocking=True) for k, v in cat.items()}
         with torch.no_grad():
             if cols_dev is not None:
                 scores = model(cat["input_ids"], cat["segment_ids"], cat["attention_mask"], img_feats=cat["img_feats"],
@@ -55,7 +97,7 @@ def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4
         for q in chunk:
             first.append(first[-1] + q["input_ids"].size(0))
         idx = scoring.select_regions_device(scores, sets, first, none_id if col_of is None else col_of[int(none_id)], few_shot=few_shot)
-        chosen[start - lo:start - lo + len(chunk)] = idx
+        chosen[_sel(idx_local, device, bucket)] = idx
     allc = cdist.gather_fixed(chosen, len(queries), fill=-1).cpu().tolist()
     out = {}
     for gi, idx in enumerate(allc):
@@ -110,40 +152,46 @@ def train_batch(model, optimizer, batches, opts, device, global_step=0):
 
 
 # ---- VG-CPT (Oscar/oscar/fewshot/vg_cpt.py; launched by cmds/vg/_fsl.sh with 16 pairs per GPU) ------------------------------------
-def _vg_cat(chunk, device, per_pair):
+def _vg_cat(chunk, device, per_pair, trim=False):
     """Concatenate pairs (dicts of prompts.assemble_vg_* arrays + img_feats) into one batch; mask_token_pos gets the pair's sequence
-    offset.  img_feats (Li, D) is repeated per sequence on the device (the reference stacks it per sequence)."""
+    offset.  img_feats (Li, D) is repeated per sequence on the device (the reference stacks it per sequence).  trim: the host arrays are cut
+    to the batch extent first (the head rows kept), and only the first Li' regions of every image are moved."""
     t = lambda x: torch.as_tensor(x)
-    out = {k: torch.cat([t(q[k]) for q in chunk], 0).to(device, non_blocking=True) for k in ("input_ids", "segment_ids", "attention_mask")}
+    out = {k: torch.cat([t(q[k]) for q in chunk], 0) for k in ("input_ids", "segment_ids", "attention_mask")}
+    pos = torch.cat([t(q["mask_token_pos"]).long() + torch.tensor([per_pair * i, 0]) for i, q in enumerate(chunk)], 0)
+    li = None
+    if trim:
+        out, li = _trim_host(out, pos)
+    out = {k: v.to(device, non_blocking=True) for k, v in out.items()}
     feats = []
     for q in chunk:
-        f = t(q["img_feats"]).to(device, non_blocking=True)
+        f = t(q["img_feats"])[..., :li, :].to(device, non_blocking=True)
         feats.append(f.unsqueeze(0).expand(per_pair, -1, -1) if f.dim() == 2 else f)
     out["img_feats"] = torch.cat(feats, 0).contiguous()
-    pos = [t(q["mask_token_pos"]).long() + torch.tensor([per_pair * i, 0]) for i, q in enumerate(chunk)]
-    out["mask_token_pos"] = torch.cat(pos, 0).to(device)
+    out["mask_token_pos"] = pos.to(device)
     return out
 
 
-def val_vg(model, pairs, idx2pred, device, batch_pairs=16):
+def val_vg(model, pairs, idx2pred, device, batch_pairs=16, trim=False, bucket=False):
     """Zero-shot / evaluation pass of vg_cpt.py:255-305.  pairs: one dict per TSV row -- ``img_key`` (the image name), ``input_ids``
     (6, Lt), ``segment_ids``, ``attention_mask`` (6, Lt + Li), ``mask_token_pos`` (12, 2) as prompts.assemble_vg_zsl gives them, and
     ``img_feats`` (Li, D) or (6, Li, D).  Pairs are sharded across ranks as val_queries shards queries; each batch is scored on the
     device (scoring.vg_predicate_scores) and the fixed-shape (pairs, 2, C) scores are gathered with one all_gather.
     Returns (scores (pairs, 2, C) fp32 on the device, keys): keys[2 i] = pair i's key, keys[2 i + 1] = its reverse_imkey -- the rows of
-    scores.view(-1, C), in dataset order, as scoring.vg_eval_table takes them."""
+    scores.view(-1, C), in dataset order, as scoring.vg_eval_table takes them.  trim / bucket: see the top of this module."""
     model.eval()
     rank, world = cdist.rank_world()
     lo, hi = cdist.shard_range(len(pairs), rank, world)
     C = max(int(i) for i in idx2pred) + 1
     local = torch.zeros((hi - lo, 2, C), dtype=torch.float32, device=device)
-    for start in range(lo, hi, batch_pairs):
-        chunk = pairs[start:min(start + batch_pairs, hi)]
-        b = _vg_cat(chunk, device, 6)
+    keys = [_item_length(q["attention_mask"], np.asarray(q["input_ids"]).shape[1]) for q in pairs[lo:hi]] if bucket else None
+    for idx in _walk(hi - lo, batch_pairs, keys):
+        chunk = [pairs[lo + i] for i in idx]
+        b = _vg_cat(chunk, device, 6, trim)
         with torch.no_grad():
             sc = scoring.vg_predicate_scores(model, b["input_ids"], b["segment_ids"], b["attention_mask"], b["img_feats"],
                                              b["mask_token_pos"], idx2pred)
-        local[start - lo:start - lo + len(chunk)] = sc
+        local[_sel(idx, device, bucket)] = sc
     scores = cdist.gather_fixed(local, len(pairs), fill=0)
     keys = []
     for q in pairs:
@@ -193,20 +241,29 @@ def train_vg_batch(model, optimizer, batches, opts, device, global_step=0):
 
 
 # ---- VCR Q->AR (Oscar/oscar/fewshot/vcr_qar_nsp_cpt.py; launched by cmds/vcr/qar_cpt_fsl.sh) ----------------------------------------------
-def _qar_blocks(chunk, device):
+def _qar_blocks(chunk, device, trim=False):
     """Concatenate questions (prompts.assemble_vcr_qar dicts + ``img_feats`` (Li, D)) into the Q->A block and the QA->R block of one batch, in
-    the reference's inputs-dict layout; img_feats is expanded per sequence on the device (vcr_collate_fn stacks it per sequence)."""
+    the reference's inputs-dict layout; img_feats is expanded per sequence on the device (vcr_collate_fn stacks it per sequence).  trim: both
+    blocks are cut on the host to ONE extent, the larger of the two (they run as one batch), and only the first Li' regions are moved."""
     t = lambda x: torch.as_tensor(x)
+    host = [{"input_ids": torch.cat([t(q[part]["input_ids"]) for q in chunk], 0),
+             "attention_mask": torch.cat([t(q[part]["input_mask"]) for q in chunk], 0),
+             "segment_ids": torch.cat([t(q[part]["segment_ids"]) for q in chunk], 0)} for part in ("q_a", "qa_r")]
+    li = None
+    if trim:
+        ext = [batching.batch_extent(b["attention_mask"], b["input_ids"].shape[1]) for b in host]
+        lt, li = max(e[0] for e in ext), max(e[1] for e in ext)
+        host = [batching.trim(b, lt, li) for b in host]
     blocks = []
-    for part in ("q_a", "qa_r"):
+    for part, b in zip(("q_a", "qa_r"), host):
         feats = []
         for q in chunk:
-            f = t(q["img_feats"]).to(device, non_blocking=True)
+            f = t(q["img_feats"])[..., :li, :].to(device, non_blocking=True)
             n = q[part]["input_ids"].shape[0]
             feats.append(f.unsqueeze(0).expand(n, -1, -1) if f.dim() == 2 else f)
-        blocks.append({"input_ids": torch.cat([t(q[part]["input_ids"]) for q in chunk], 0).to(device, non_blocking=True),
-                       "attention_mask": torch.cat([t(q[part]["input_mask"]) for q in chunk], 0).to(device, non_blocking=True),
-                       "token_type_ids": torch.cat([t(q[part]["segment_ids"]) for q in chunk], 0).to(device, non_blocking=True),
+        blocks.append({"input_ids": b["input_ids"].to(device, non_blocking=True),
+                       "attention_mask": b["attention_mask"].to(device, non_blocking=True),
+                       "token_type_ids": b["segment_ids"].to(device, non_blocking=True),
                        "img_feats": torch.cat(feats, 0).float().contiguous()})
     return blocks
 
@@ -218,12 +275,13 @@ def _qar_layout(questions):
     return n_ans, n_rats
 
 
-def val_vcr_qar(model, questions, device, batch_questions=4):
+def val_vcr_qar(model, questions, device, batch_questions=4, trim=False, bucket=False):
     """Evaluation pass of vcr_qar_nsp_cpt.py:605-703 (evaluate) on VCRQAR_NSPCPT.  questions: prompts.assemble_vcr_qar dicts with ``img_feats``
     (Li, D).  Questions are sharded over ranks (whole questions per rank); per batch ONE encoder pass runs over both blocks (qar_forward) and the
     choice runs on the device (cpt_vcr_qar_choose); the fixed-shape (n_q, 2) predictions, (n_q, 3) flags and (n_q, n_ans + n_rats) choice scores
     are gathered to every rank.  Accuracies follow the reference: results de-duplicated by questionId (last wins), divided by the number of
-    questions; "q_ar" is the reference's "Eval Accuracy".  Returns {"preds", "flags", "scores", "q_ids", "acc": {"q_a", "qa_r", "q_ar"}}."""
+    questions; "q_ar" is the reference's "Eval Accuracy".  Returns {"preds", "flags", "scores", "q_ids", "acc": {"q_a", "qa_r", "q_ar"}}.
+    trim / bucket: see the top of this module."""
     model.eval()
     n_ans, n_rats = _qar_layout(questions)
     rank, world = cdist.rank_world()
@@ -231,18 +289,20 @@ def val_vcr_qar(model, questions, device, batch_questions=4):
     preds = torch.full((hi - lo, 2), -1, dtype=torch.int64, device=device)
     flags = torch.zeros((hi - lo, 3), dtype=torch.uint8, device=device)
     scores = torch.zeros((hi - lo, n_ans + n_rats), dtype=torch.float32, device=device)
-    for start in range(lo, hi, batch_questions):
-        chunk = questions[start:min(start + batch_questions, hi)]
-        qa, qr = _qar_blocks(chunk, device)
+    keys = None
+    if bucket:
+        keys = [max(_item_length(q[part]["input_mask"], q[part]["input_ids"].shape[1]) for part in ("q_a", "qa_r")) for q in questions[lo:hi]]
+    for idx in _walk(hi - lo, batch_questions, keys):
+        chunk = [questions[lo + i] for i in idx]
+        qa, qr = _qar_blocks(chunk, device, trim)
         with torch.no_grad():
             _, _, sc = model.qar_forward(qa, qr, return_scores=True)
         nq = len(chunk)
         B0 = nq * n_ans
         p, f = scoring.vcr_qar_choose_device(sc[:B0], sc[B0:], [q["label"][0] for q in chunk], [q["label"][1] for q in chunk], n_ans, n_rats)
-        i = start - lo
-        preds[i:i + nq], flags[i:i + nq] = p, f
-        scores[i:i + nq, :n_ans] = sc[:B0].view(nq, n_ans)
-        scores[i:i + nq, n_ans:] = sc[B0:].view(nq, n_rats)
+        sel = _sel(idx, device, bucket)
+        preds[sel], flags[sel] = p, f
+        scores[sel] = torch.cat([sc[:B0].view(nq, n_ans), sc[B0:].view(nq, n_rats)], 1)
     n = len(questions)
     preds = cdist.gather_fixed(preds, n, fill=-1).cpu()
     flags = cdist.gather_fixed(flags, n, fill=0).cpu()
@@ -301,14 +361,14 @@ def _seq_feats(f, n, device):
     return f.unsqueeze(0).expand(n, -1, -1) if f.dim() == 2 else f
 
 
-def val_gqa(model, questions, labels, tokenizer, device, batch_questions=256):
+def val_gqa(model, questions, labels, tokenizer, device, batch_questions=256, trim=False, bucket=False):
     """Evaluation pass of gqa_cpt.py:558-636 (evaluate) on REC_MLM_CPT.  questions: prompts.assemble_gqa dicts with ``img_feats`` (Li, D) and
     ``igt``, the question's ground-truth label indices (eval_dic[str(q_id)]); labels: the data set's answer strings.  Questions are sharded over
     ranks; per batch ONE forward scores the label columns only (vocab_columns = every label's first word-piece id, duplicates kept) at the first
     [MASK] slot, and the argmax, the multi-ground-truth correctness and their count run in one launch (cpt_gqa_choose); the fixed-shape
     predictions, flags and (n, C) logits are gathered to every rank.  Accuracy as the reference: results de-duplicated by question_id (last
     wins), divided by the number of questions.  Returns {"preds" (n,) label columns, "answers" [the first-piece strings the reference reports],
-    "correct" (n,) uint8, "logits" (n, C), "q_ids", "acc"}."""
+    "correct" (n,) uint8, "logits" (n, C), "q_ids", "acc"}.  trim / bucket: see the top of this module."""
     model.eval()
     token_ids, label_sid, piece_sid = scoring.gqa_string_ids(labels, tokenizer)
     _, answer_labels = scoring.gqa_first_pieces(labels, tokenizer)
@@ -322,18 +382,22 @@ def val_gqa(model, questions, labels, tokenizer, device, batch_questions=256):
     correct = torch.zeros((hi - lo,), dtype=torch.uint8, device=device)
     logits = torch.zeros((hi - lo, C), dtype=torch.float32, device=device)
     t = lambda x: torch.as_tensor(x)
-    for start in range(lo, hi, batch_questions):
-        chunk = questions[start:min(start + batch_questions, hi)]
-        ids = torch.stack([t(q["input_ids"]) for q in chunk]).to(device, non_blocking=True)
-        seg = torch.stack([t(q["segment_ids"]) for q in chunk]).to(device, non_blocking=True)
-        msk = torch.stack([t(q["input_mask"]) for q in chunk]).to(device, non_blocking=True)
-        feats = torch.stack([t(q["img_feats"]) for q in chunk]).to(device, non_blocking=True).float()
-        mpos = torch.tensor([int(q["mask_token_pos"][0]) for q in chunk], dtype=torch.int64).to(device, non_blocking=True)   # raw_batch[-1][0]
+    keys = [_item_length(np.asarray(q["input_mask"])[None], np.asarray(q["input_ids"]).shape[0]) for q in questions[lo:hi]] if bucket else None
+    for idx in _walk(hi - lo, batch_questions, keys):
+        chunk = [questions[lo + i] for i in idx]
+        b = {"input_ids": torch.stack([t(q["input_ids"]) for q in chunk]), "segment_ids": torch.stack([t(q["segment_ids"]) for q in chunk]),
+             "attention_mask": torch.stack([t(q["input_mask"]) for q in chunk]), "img_feats": torch.stack([t(q["img_feats"]) for q in chunk])}
+        mpos = torch.tensor([int(q["mask_token_pos"][0]) for q in chunk], dtype=torch.int64)    # raw_batch[-1][0]
+        if trim:
+            b = _trim_host(b, mpos)[0]
+        ids, seg, msk = (b[k].to(device, non_blocking=True) for k in ("input_ids", "segment_ids", "attention_mask"))
+        feats = b["img_feats"].to(device, non_blocking=True).float()
+        mpos = mpos.to(device, non_blocking=True)
         with torch.no_grad():
             sc = model(ids, seg, msk, img_feats=feats, mask_token_pos=mpos, vocab_columns=cols)[0]
-        p, c = scoring.gqa_choose_device(sc, piece, gt_all[start:start + len(chunk)])
-        i = start - lo
-        preds[i:i + len(chunk)], correct[i:i + len(chunk)], logits[i:i + len(chunk)] = p, c, sc
+        p, c = scoring.gqa_choose_device(sc, piece, gt_all[torch.as_tensor(idx) + lo])
+        sel = _sel(idx, device, bucket)
+        preds[sel], correct[sel], logits[sel] = p, c, sc
     n = len(questions)
     preds = cdist.gather_fixed(preds, n, fill=-1).cpu()
     correct = cdist.gather_fixed(correct, n, fill=0).cpu()
@@ -429,16 +493,22 @@ def _gqa_pass(model, optimizer, scheduler, batches, opts, device, label_token_id
     return _accumulate(model, optimizer, scheduler, micro(), opts, global_step, use_device_clip)
 
 
-def _vcr_block(chunk, device):
-    """Questions (prompts.assemble_vcr dicts + ``img_feats`` (Li, D)) concatenated in vcr_collate_fn's layout: one row per answer choice."""
+def _vcr_block(chunk, device, trim=False):
+    """Questions (prompts.assemble_vcr dicts + ``img_feats`` (Li, D)) concatenated in vcr_collate_fn's layout: one row per answer choice.
+    trim: the host arrays are cut to the batch extent first, and only the first Li' regions of every image are moved."""
     t = lambda x: torch.as_tensor(x)
     interval = chunk[0]["input_ids"].shape[0]
     if any(q["input_ids"].shape[0] != interval for q in chunk):
         raise ValueError("VCR Q->A: every question of a pass needs the same number of answer choices")
-    return {"input_ids": torch.cat([t(q["input_ids"]) for q in chunk], 0).to(device, non_blocking=True),
-            "attention_mask": torch.cat([t(q["input_mask"]) for q in chunk], 0).to(device, non_blocking=True),
-            "token_type_ids": torch.cat([t(q["segment_ids"]) for q in chunk], 0).to(device, non_blocking=True),
-            "img_feats": torch.cat([_seq_feats(q["img_feats"], interval, device) for q in chunk], 0).float().contiguous()}, interval
+    b = {"input_ids": torch.cat([t(q["input_ids"]) for q in chunk], 0), "attention_mask": torch.cat([t(q["input_mask"]) for q in chunk], 0),
+         "segment_ids": torch.cat([t(q["segment_ids"]) for q in chunk], 0)}
+    li = None
+    if trim:
+        b, li = _trim_host(b)
+    return {"input_ids": b["input_ids"].to(device, non_blocking=True),
+            "attention_mask": b["attention_mask"].to(device, non_blocking=True),
+            "token_type_ids": b["segment_ids"].to(device, non_blocking=True),
+            "img_feats": torch.cat([_seq_feats(t(q["img_feats"])[..., :li, :], interval, device) for q in chunk], 0).float().contiguous()}, interval
 
 
 def _vcr_label(q):
@@ -446,12 +516,13 @@ def _vcr_label(q):
     return int(lb[0] if isinstance(lb, (list, tuple)) else lb)
 
 
-def val_vcr(model, questions, device, batch_questions=8):
+def val_vcr(model, questions, device, batch_questions=8, trim=False, bucket=False):
     """Evaluation pass of vcr_nsp_cpt.py:583-620 (evaluate) on NSPCPT.  questions: prompts.assemble_vcr dicts with ``img_feats`` (Li, D).
     Questions are sharded over ranks (whole questions per rank); per batch one forward gives the relation scores and ONE launch
     (cpt_nsp_choose) the choice scores 1 - softmax(rel)[:, 1], each question's argmax and its correctness; the fixed-shape predictions, flags
     and (n_q, interval) choice scores are gathered to every rank.  Accuracy as the reference: results de-duplicated by questionId (last wins),
-    divided by the number of questions.  Returns {"preds" (n_q,), "correct" (n_q,) uint8, "scores" (n_q, interval), "q_ids", "acc"}."""
+    divided by the number of questions.  Returns {"preds" (n_q,), "correct" (n_q,) uint8, "scores" (n_q, interval), "q_ids", "acc"}.
+    trim / bucket: see the top of this module."""
     model.eval()
     interval = questions[0]["input_ids"].shape[0]
     rank, world = cdist.rank_world()
@@ -459,16 +530,17 @@ def val_vcr(model, questions, device, batch_questions=8):
     preds = torch.full((hi - lo,), -1, dtype=torch.int64, device=device)
     correct = torch.zeros((hi - lo,), dtype=torch.uint8, device=device)
     scores = torch.zeros((hi - lo, interval), dtype=torch.float32, device=device)
-    for start in range(lo, hi, batch_questions):
-        chunk = questions[start:min(start + batch_questions, hi)]
-        b, iv = _vcr_block(chunk, device)
+    keys = [_item_length(q["input_mask"], q["input_ids"].shape[1]) for q in questions[lo:hi]] if bucket else None
+    for idx in _walk(hi - lo, batch_questions, keys):
+        chunk = [questions[lo + i] for i in idx]
+        b, iv = _vcr_block(chunk, device, trim)
         if iv != interval:
             raise ValueError("VCR Q->A: every question of a pass needs the same number of answer choices")
         with torch.no_grad():
             rel = model(b["input_ids"], b["token_type_ids"], b["attention_mask"], img_feats=b["img_feats"])[0]
         sc, p, c = scoring.nsp_choose_device(rel, interval, [_vcr_label(q) for q in chunk])
-        i, nq = start - lo, len(chunk)
-        preds[i:i + nq], correct[i:i + nq], scores[i:i + nq] = p, c, sc.view(nq, interval)
+        sel = _sel(idx, device, bucket)
+        preds[sel], correct[sel], scores[sel] = p, c, sc.view(len(chunk), interval)
     n = len(questions)
     preds = cdist.gather_fixed(preds, n, fill=-1).cpu()
     correct = cdist.gather_fixed(correct, n, fill=0).cpu()

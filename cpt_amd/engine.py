@@ -90,6 +90,7 @@ class PackedModel(object):
         self._fold = None
         self._fold_stale = True
         self.pending = None         # data-parallel optimizer whose parameter all-gather is still in flight (train.FusedAdamW)
+        self.last_shape = None      # (B, Lt, Li) the last inference forward ran on: the padded shape, or what trim=True cut it to
 
     # ---- packing -------------------------------------------------------------------------
     def _named(self):
@@ -442,13 +443,14 @@ class PackedModel(object):
         return w("cls_ans.weight"), v("cls_ans.bias"), w("cls_rat.weight"), v("cls_rat.bias")
 
     def forward_rel2(self, input_ids, token_type_ids=None, attention_mask=None, position_ids=None, img_feats=None, B0=None, labels=None,
-                     labels_host=None):
+                     labels_host=None, trim=False):
         """VCR Q->AR on one batch: rows [0, B0) through head 0 (cls_ans), rows [B0, B) through head 1 (cls_rat), one encoder pass
         (cpt_model_fwd with CPT_OUT_POOLED), then the two heads in one launch (cpt_rel2_scores).  Returns {"rel": (B, n_rel), "score": (B,)
-        = 1 - softmax(rel)[:, 1], and with labels "loss": group-0 mean + group-1 mean (0-dim), "loss2": the two means}."""
+        = 1 - softmax(rel)[:, 1], and with labels "loss": group-0 mean + group-1 mean (0-dim), "loss2": the two means}.
+        trim: as in ``forward`` (the encoder pass returns the pooled [CLS] rows only)."""
         if self.head != "qar":
             raise RuntimeError("cpt_amd: forward_rel2 belongs to the VCR Q->AR model (head 'qar'), not '%s'" % self.head)
-        out = self.forward(input_ids, token_type_ids, attention_mask, position_ids, img_feats, flags=L.OUT_POOLED)
+        out = self.forward(input_ids, token_type_ids, attention_mask, position_ids, img_feats, flags=L.OUT_POOLED, trim=trim)
         pooled = out["pooled"]
         B = pooled.size(0)
         B0 = B if B0 is None else int(B0)
@@ -494,9 +496,39 @@ class PackedModel(object):
             self._ws["fwd"] = ws
         return ws
 
+    def _trim_batch(self, input_ids, token_type_ids, attention_mask, position_ids, img_feats, head_pos):
+        """trim=True on a padded device batch with a 2-D mask: cut the batch to the part some sequence attends to (include/cpt_hip.h
+        cpt_batch_extents, cpt_trim_batch; the rules are those of batching.batch_extent).  The extents are two int32 read back from the
+        device: ONE small synchronisation of the current stream per forward -- a loop that cannot afford it trims on the host before its copy
+        (batching.trim, as the drivers do) and leaves trim off here.  A batch that is attended to its last column is returned as it came."""
+        B, Lt = input_ids.shape
+        Li = img_feats.size(1) if img_feats is not None else 0
+        dev = input_ids.device
+        st = L.stream_ptr()
+        ext = self._ws.get("ext")
+        if ext is None or ext.device != dev:
+            ext = torch.zeros(2, device=dev, dtype=torch.int32)
+            self._ws["ext"] = ext
+        L.check(L.lib().cpt_batch_extents(attention_mask.data_ptr(), B, Lt, Li, L.ptr(head_pos), head_pos.numel() if head_pos is not None else 0,
+                                          ext.data_ptr(), st), "cpt_batch_extents")
+        lt2, li2 = ext.tolist()
+        if (lt2, li2) == (Lt, Li):
+            return input_ids, token_type_ids, attention_mask, position_ids, img_feats
+        new = lambda t, *shape: None if t is None else torch.empty(shape, device=dev, dtype=t.dtype)
+        ids2, tt2, pos2 = new(input_ids, B, lt2), new(token_type_ids, B, lt2), new(position_ids, B, lt2)
+        mask2 = new(attention_mask, B, lt2 + li2)
+        feats2 = new(img_feats, B, li2, img_feats.size(2)) if li2 > 0 else None
+        L.check(L.lib().cpt_trim_batch(input_ids.data_ptr(), L.ptr(token_type_ids), L.ptr(position_ids), attention_mask.data_ptr(), L.ptr(img_feats),
+                                       B, Lt, Li, img_feats.size(2) if img_feats is not None else 0, lt2, li2, ids2.data_ptr(), L.ptr(tt2),
+                                       L.ptr(pos2), mask2.data_ptr(), L.ptr(feats2), st), "cpt_trim_batch")
+        return ids2, tt2, mask2, pos2, feats2
+
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, position_ids=None, img_feats=None,
-                mask_pos=None, labels=None, flags=0, logit_cols=None):
+                mask_pos=None, labels=None, flags=0, logit_cols=None, trim=False):
         """Returns dict with the outputs selected by `flags` (see _lib.OUT_*).
+        trim (default off): run the encoder on the part of the padded batch that some sequence attends to (_trim_batch; one small
+        synchronisation).  Head-row outputs only: silently skipped with a 3-D mask, without a mask, with OUT_SEQ / OUT_ALL_LOGITS (a dropped
+        row would be visible), with a loss or labels, and with OUT_MASK_LOGITS but no mask_pos.  ``last_shape`` holds the shape that ran.
         logit_cols (1-D int64 tensor of vocabulary ids, with OUT_MASK_LOGITS and no loss): ``logits`` holds those columns only, (B, len(logit_cols)),
         in list order -- the decoder then reads len(logit_cols) rows of its table instead of streaming it (cpt_outputs.logit_cols)."""
         if self.head == "qar" and flags & L.OUT_REL:
@@ -536,6 +568,13 @@ class PackedModel(object):
         if attention_mask is not None and tuple(attention_mask.shape) != want:
             raise RuntimeError("cpt_amd: attention_mask shape %s != %s" % (tuple(attention_mask.shape), want))
         call_flags = flags | (L.ATTN_MASK_3D if mask3 else 0)      # (B, L, L): one mask row per query (modeling_bert.py:215-216)
+        if (trim and attention_mask is not None and not mask3 and labels is None and not flags & (L.OUT_SEQ | L.OUT_ALL_LOGITS | L.OUT_LOSS)
+                and (mask_pos is not None or not flags & L.OUT_MASK_LOGITS)):
+            input_ids, token_type_ids, attention_mask, position_ids, img_feats = self._trim_batch(
+                input_ids, token_type_ids, attention_mask, position_ids, img_feats, mask_pos if flags & L.OUT_MASK_LOGITS else None)
+            Lt = input_ids.size(1)
+            Li = img_feats.size(1) if img_feats is not None else 0
+        self.last_shape = (B, Lt, Li)
         m, _ = self.descriptor()
         H, V = self.cfg.hidden_size, self.cfg.vocab_size
         out = {}
@@ -579,10 +618,11 @@ class PackedModel(object):
         return out
 
     def forward_rows(self, input_ids, token_type_ids=None, attention_mask=None, position_ids=None, img_feats=None,
-                     row_seq=None, mask_pos=None, cols=None, lse=True):
+                     row_seq=None, mask_pos=None, cols=None, lse=True, trim=False):
         """MLM head on n head rows (include/cpt_hip.h cpt_model_fwd_rows): row r is position mask_pos[r] of sequence row_seq[r]
         (row_seq ascending, any number of rows per sequence).  Returns {"logits": (n, len(cols)) -- or (n, V) without cols --,
-        "lse": (n,) natural-log log-sum-exp of each row over all V columns (None with lse=False)}."""
+        "lse": (n,) natural-log log-sum-exp of each row over all V columns (None with lse=False)}.
+        trim: as in ``forward`` (skipped with a 3-D mask or without a mask)."""
         self.ensure_packed()
         self.refresh_shadow()
         if self.dtype == "bf16" and self.fold_ln:
@@ -619,6 +659,12 @@ class PackedModel(object):
         want = (B, Lseq, Lseq) if mask3 else (B, Lseq)
         if attention_mask is not None and tuple(attention_mask.shape) != want:
             raise RuntimeError("cpt_amd: attention_mask shape %s != %s" % (tuple(attention_mask.shape), want))
+        if trim and attention_mask is not None and not mask3:
+            input_ids, token_type_ids, attention_mask, position_ids, img_feats = self._trim_batch(
+                input_ids, token_type_ids, attention_mask, position_ids, img_feats, mask_pos)
+            Lt = input_ids.size(1)
+            Li = img_feats.size(1) if img_feats is not None else 0
+        self.last_shape = (B, Lt, Li)
         V = self.cfg.vocab_size
         n = row_seq.numel()
         if cols is not None:

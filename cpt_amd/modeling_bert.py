@@ -106,6 +106,10 @@ def _check_unsupported(config, head_mask, encoder_history_states):
 class _EngineMixin(object):
     """compute dtype switch + lazily built PackedModel."""
     _head = "none"
+    # Length-aware evaluation (extension; README "Length-aware evaluation"): True makes every inference forward of this model run the encoder on
+    # the part of the padded batch some sequence attends to (PackedModel.forward trim=True: one small synchronisation per forward; skipped for
+    # outputs that return every position, 3-D masks, losses and training).  A reference-style loop gets it by setting this one attribute.
+    trim_padding = False
 
     def _engine(self):
         eng = self.__dict__.get("_cpt_engine")
@@ -159,7 +163,7 @@ class BertImgModel(_EngineMixin, BertPreTrainedModel):
                 img_feats=None, encoder_history_states=None):
         _check_unsupported(self.config, head_mask, encoder_history_states)
         out = self._engine().forward(input_ids, token_type_ids, attention_mask, position_ids, img_feats,
-                                     flags=L.OUT_SEQ | L.OUT_POOLED)
+                                     flags=L.OUT_SEQ | L.OUT_POOLED, trim=self.trim_padding)
         return (out["seq"], out["pooled"])
 
 
@@ -186,7 +190,7 @@ class BertImgForPreTraining(_EngineMixin, ImgPreTrainedModel):
         if want_loss:
             flags |= L.OUT_LOSS
         out = self._engine().forward(input_ids, token_type_ids, attention_mask, position_ids, img_feats,
-                                     labels=masked_lm_labels if want_loss else None, flags=flags)
+                                     labels=masked_lm_labels if want_loss else None, flags=flags, trim=self.trim_padding)
         outputs = (out["logits"], out["rel"])
         if want_loss:
             outputs = (out["loss"],) + outputs + (out["loss"],)

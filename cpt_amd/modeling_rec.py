@@ -85,7 +85,7 @@ class REC_MLM_CPT(_EngineMixin, BertPreTrainedModel):
             return mlm_loss_with_grad(self, input_ids, token_type_ids, attention_mask, labels, position_ids,
                                       img_feats, mask_token_pos)
         out = self._engine().forward(input_ids, token_type_ids, attention_mask, position_ids, img_feats,
-                                     mask_pos=mask_token_pos, labels=labels, flags=flags, logit_cols=vocab_columns)
+                                     mask_pos=mask_token_pos, labels=labels, flags=flags, logit_cols=vocab_columns, trim=self.trim_padding)
         outputs = (out["logits"],)
         if masked_lm_labels is not None:
             outputs = (out["loss"],) + outputs
@@ -110,7 +110,7 @@ class REC_MLM_CPT(_EngineMixin, BertPreTrainedModel):
             order = torch.argsort(seq, stable=True)        # the library takes the rows grouped by ascending sequence
             seq, pos = seq[order], pos[order]
         out = self._engine().forward_rows(input_ids, token_type_ids, attention_mask, position_ids, img_feats, row_seq=seq,
-                                          mask_pos=pos, cols=vocab_columns, lse=log_softmax)
+                                          mask_pos=pos, cols=vocab_columns, lse=log_softmax, trim=self.trim_padding)
         scores = out["logits"]
         if log_softmax:
             scores = scores - out["lse"][:, None]

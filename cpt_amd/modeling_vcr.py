@@ -57,7 +57,7 @@ class NSPCPT(_EngineMixin, BertPreTrainedModel):
             from .train import mlm_loss_with_grad
             return mlm_loss_with_grad(self, input_ids, token_type_ids, attention_mask, next_sentence_label.view(-1),
                                       position_ids, img_feats, None)
-        out = self._engine().forward(input_ids, token_type_ids, attention_mask, position_ids, img_feats, flags=L.OUT_REL)
+        out = self._engine().forward(input_ids, token_type_ids, attention_mask, position_ids, img_feats, flags=L.OUT_REL, trim=self.trim_padding)
         rel = out["rel"]
         outputs = (rel,)
         if next_sentence_label is not None:
@@ -132,7 +132,8 @@ class VCRQAR_NSPCPT(_EngineMixin, BertPreTrainedModel):
                                       rel2=(B0, _host_labels(lab)))
         out = self._engine().forward_rel2(input_ids, token_type_ids, attention_mask, position_ids, img_feats, B0=B0,
                                           labels=None if next_sentence_label is None else next_sentence_label.view(-1),
-                                          labels_host=None if next_sentence_label is None else _host_labels(next_sentence_label.view(-1)))
+                                          labels_host=None if next_sentence_label is None else _host_labels(next_sentence_label.view(-1)),
+                                          trim=self.trim_padding)
         outputs = (out["rel"],)
         if next_sentence_label is not None:
             outputs = (out["loss"],) + outputs
@@ -172,7 +173,7 @@ class VCRQAR_NSPCPT(_EngineMixin, BertPreTrainedModel):
             from .train import mlm_loss_with_grad
             loss, rel = mlm_loss_with_grad(self, ids, tt, mask, labels, None, feats, None, rel2=(B0, labels_host))
             return loss, rel[:B0], rel[B0:]
-        out = self._engine().forward_rel2(ids, tt, mask, None, feats, B0=B0, labels=labels, labels_host=labels_host)
+        out = self._engine().forward_rel2(ids, tt, mask, None, feats, B0=B0, labels=labels, labels_host=labels_host, trim=self.trim_padding)
         rel = out["rel"]
         res = (rel[:B0], rel[B0:])
         if labels is not None:

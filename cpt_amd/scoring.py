@@ -207,7 +207,7 @@ def vg_predicate_scores(model, input_ids, segment_ids, attention_mask, img_feats
     B = input_ids.size(0)
     slot_row = vg_slot_rows_from(mask_token_pos[:, 0], B)
     out = model._engine().forward_rows(input_ids, segment_ids, attention_mask, None, img_feats, row_seq=mask_token_pos[:, 0],
-                                       mask_pos=mask_token_pos[:, 1], cols=cols.to(dev), lse=True)
+                                       mask_pos=mask_token_pos[:, 1], cols=cols.to(dev), lse=True, trim=model.trim_padding)
     n_pairs = B // 6
     sc = mean_logprob_scores_device(out["logits"], out["lse"], slot_row, cand_cols, cand_len)
     return sc.view(n_pairs, 2, -1)

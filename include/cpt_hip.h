@@ -306,6 +306,25 @@ size_t cpt_grad_clip_workspace_bytes(void);
 int cpt_grad_clip(float* g, size_t n, float max_norm, const double* sq_in, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Length-aware evaluation: trim a padded batch to the part any sequence attends to.  Added beside ABI 8, no struct changed.
+ * A position whose mask column is 0 in every sequence of the batch is never a key, and its own row is read by no head-row output ([MASK]
+ * rows, [CLS] row): dropping it changes only the order of the sums.  Not for outputs that return every position, 3-D masks or training.
+ * ---------------------------------------------------------------------------------------- */
+/* out [2] int32 (device) = {Lt', Li'} of attn_mask [B][Lt + Li] int64 (device): per part (text: columns [0, Lt), regions: [Lt, Lt + Li)) 1 +
+ * the last column that is non-zero in any sequence, 0 when there is none -- no prefix form assumed, a hole stays inside.  Lt' >= 1 always.
+ * mask_pos [n_pos] int64 (device, optional): head-row positions in [0, Lt + Li); a text position p gives Lt' >= p + 1, a region position keeps
+ * the text whole (Lt' = Lt) and gives Li' >= p - Lt + 1, a position outside the sequence keeps both parts whole.  One memset node and one
+ * launch, integer max only (the result does not depend on the order of arrival), no host work. */
+int cpt_batch_extents(const int64_t* attn_mask, int B, int Lt, int Li, const int64_t* mask_pos, int n_pos, int32_t* out, void* stream);
+/* One launch: the contiguous copies input_ids_out / token_type_out / position_ids_out [B][Lt_out] (columns [0, Lt_out) of the [B][Lt] inputs;
+ * token_type and position_ids optional, each with its output), attn_mask_out [B][Lt_out + Li_out] (text columns [0, Lt_out), then region columns
+ * [Lt, Lt + Li_out) of the [B][Lt + Li] mask) and img_feats_out [B][Li_out][img_dim] fp32 (regions [0, Li_out) of [B][Li][img_dim]; not touched
+ * when Li_out == 0).  1 <= Lt_out <= Lt, 0 <= Li_out <= Li.  Feature rows move as 16-byte accesses from 8-byte boundaries when img_dim is even. */
+int cpt_trim_batch(const int64_t* input_ids, const int64_t* token_type, const int64_t* position_ids, const int64_t* attn_mask, const float* img_feats,
+                   int B, int Lt, int Li, int img_dim, int Lt_out, int Li_out, int64_t* input_ids_out, int64_t* token_type_out,
+                   int64_t* position_ids_out, int64_t* attn_mask_out, float* img_feats_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Few-shot training step (Oscar/oscar/fewshot/refcoco_cpt.py:231-249): forward that keeps the
  * activations, backward into caller-owned fp32 gradient tensors laid out like the parameters,
  * fused AdamW.  [MASK]-rows mode only (the loss of modeling_rec.py:147-150 sees only those rows).
