@@ -1,6 +1,6 @@
 """Driver-side hot loops on the HIP path: counterparts of the reference's ``val`` and ``train_batch``.
 
-  * ``val_queries``  <- /root/reference/Oscar/oscar/zeroshot/refcoco_cpt.py:208-288 (and the few-shot
+  * ``val_queries``  <- Oscar/oscar/zeroshot/refcoco_cpt.py:208-288 (and the few-shot
     variant fewshot/refcoco_cpt.py:258-315): per query, score every proposal sequence at its [MASK]
     slot, gather the colour logits, argmax -> chosen rectangle; queries are sharded across ranks and
     the chosen indices are gathered with one fixed-shape all_gather.
@@ -22,7 +22,11 @@ from .train import get_lr_sched
 logger = logging.getLogger(__name__)
 
 
-# ---- length-aware evaluation (batching.py): options of the val_* drivers, all off by default ----------------------------------------------------
+# ---- the evaluation pass every val_* driver runs (_eval_pass) --------------------------------------------------------------------------------
+#   Items (queries, pairs, questions) are sharded over ranks, whole items per rank (dist.shard_range); each rank walks ITS shard in groups
+#   (_walk), the driver's ``step`` scores one group -- batch, one forward, one choice kernel -- and the results go into fixed-shape shard-local
+#   tensors that one all_gather per output brings to every rank (dist.gather_fixed).  A driver holds its constants, its ``step`` and what it
+#   makes of the gathered tensors.  Length-aware evaluation (batching.py), all off by default:
 #   trim    the host arrays of every batch are cut to the part some sequence attends to BEFORE the H2D copy (batching.trim: no device copy, fewer
 #           PCIe bytes); the encoder then runs on (B, Lt' + Li').  Head-row outputs only, which is all these drivers read.
 #   bucket  each rank walks ITS shard by ascending length (batching.length_order; an item of several sequences -- a query, a VCR question, a VG
@@ -33,15 +37,53 @@ def _item_length(mask, Lt):
     return int((t + r).max())
 
 
-def _walk(n, size, keys=None):
-    """Lists of shard-local item indices, ``size`` per batch: in data set order, or (keys: bucket) by ascending length key, stable."""
+def _walk(n, size, keys=None, counts=None, cap=None):
+    """Lists of shard-local item indices: in data set order, or (keys: bucket) by ascending length key, stable.  ``size`` items per list -- or
+    (cap: max_sequences) whole items of counts[i] sequences each, consecutive in that order, at most cap sequences per list
+    (batching.pack_queries)."""
     order = list(range(n)) if keys is None else batching.length_order(keys, 0)[0].tolist()
-    return [order[i:i + size] for i in range(0, n, size)]
+    if cap is None:
+        return [order[i:i + size] for i in range(0, n, size)]
+    return [[order[i] for i in g] for g in batching.pack_queries([counts[i] for i in order], cap)]
 
 
 def _sel(idx, device, bucket):
     """Where the results of the items ``idx`` go in a shard-local result tensor: a slice in data set order, an index tensor under bucket."""
     return torch.as_tensor(idx, device=device) if bucket else slice(idx[0], idx[-1] + 1)
+
+
+def _eval_pass(n_items, groups_of, outputs, step, device, bucket):
+    """One sharded evaluation pass over n_items.  outputs: one (trailing shape, dtype, fill) per result tensor; groups_of(lo, hi) -> the lists
+    of shard-local indices of this rank's shard [lo, hi) (_walk); step(idx_local, lo) -> one tensor per output for those items, run under
+    no_grad.  Returns the (n_items, ...) tensors gathered to every rank, on the device, in the order of ``outputs``."""
+    rank, world = cdist.rank_world()
+    lo, hi = cdist.shard_range(n_items, rank, world)
+    local = [torch.full((hi - lo,) + tuple(shape), fill, dtype=dtype, device=device) for shape, dtype, fill in outputs]
+    for idx in groups_of(lo, hi):
+        with torch.no_grad():
+            res = step(idx, lo)
+        sel = _sel(idx, device, bucket)
+        for t, r in zip(local, res):
+            t[sel] = r
+    return tuple(cdist.gather_fixed(t, n_items, fill=o[2]) for t, o in zip(local, outputs))
+
+
+def _dedup_accuracy(flags, q_ids, n):
+    """The reference's accuracy over results keyed by question id (results_dic = {k["questionId"]: k ...}: the last entry of an id wins;
+    vcr_qar_nsp_cpt.py:682, gqa_cpt.py:619, vcr_nsp_cpt.py:619): the flags of the kept entries summed, divided by the number of questions n.
+    flags (len(q_ids),) -> float; (len(q_ids), k) -> k floats, one per column."""
+    last = {}
+    for i, qid in enumerate(q_ids):
+        last[qid] = i
+    kept = flags[sorted(last.values())].sum(0)
+    return [float(v) / n for v in kept.tolist()] if kept.dim() else float(kept.item()) / n
+
+
+def _seq_feats(f, n, device, li=None):
+    """img_feats of one item on the device: the first li regions (all of them without li) are moved, and (Li, D) is expanded to the item's n
+    sequences there (the collate functions stack it per sequence)."""
+    f = torch.as_tensor(f)[..., :li, :].to(device, non_blocking=True)
+    return f.unsqueeze(0).expand(n, -1, -1) if f.dim() == 2 else f
 
 
 def _trim_host(b, head_pos=None):
@@ -61,34 +103,26 @@ def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4
     trim / bucket: length-aware evaluation, see the top of this module.  max_sequences: batches are consecutive groups of whole queries with at
     most that many proposal sequences (batching.pack_queries) instead of ``batch_queries`` queries each -- even launches for ragged queries."""
     model.eval()
-    rank, world = cdist.rank_world()
-    lo, hi = cdist.shard_range(len(queries), rank, world)
-    chosen = torch.full((hi - lo,), -1, dtype=torch.int64, device=device)
     col_ids, col_of, cols_dev = None, None, None
     if colour_columns_only:
         col_ids = sorted({int(c) for q in queries for s in q["colors"] for c in s} | {int(none_id)})
         col_of = {c: i for i, c in enumerate(col_ids)}
         cols_dev = torch.tensor(col_ids, dtype=torch.int64, device=device)
-    order = list(range(hi - lo))
-    if bucket:
-        order = batching.length_order([_item_length(q["attention_mask"], q["input_ids"].shape[1]) for q in queries[lo:hi]], 0)[0].tolist()
-    if max_sequences is not None:
-        groups = [[order[i] for i in g] for g in batching.pack_queries([queries[lo + i]["input_ids"].size(0) for i in order], max_sequences)]
-    else:
-        groups = [order[i:i + batch_queries] for i in range(0, hi - lo, batch_queries)]
-    for idx_local in groups:
+
+    def groups_of(lo, hi):
+        shard = queries[lo:hi]
+        keys = [_item_length(q["attention_mask"], q["input_ids"].shape[1]) for q in shard] if bucket else None
+        counts = [q["input_ids"].size(0) for q in shard] if max_sequences is not None else None
+        return _walk(hi - lo, batch_queries, keys, counts, max_sequences)
+
+    def step(idx_local, lo):
         chunk = [queries[lo + i] for i in idx_local]
         cat = {k: torch.cat([q[k] for q in chunk], 0) for k in ("img_feats", "input_ids", "segment_ids", "attention_mask", "mask_token_pos")}
         if trim:
             cat = _trim_host(cat, cat["mask_token_pos"])[0]
         cat = {k: v.to(device, non_blocking=True) for k, v in cat.items()}
-        with torch.no_grad():
-            if cols_dev is not None:
-                scores = model(cat["input_ids"], cat["segment_ids"], cat["attention_mask"], img_feats=cat["img_feats"],
-                               mask_token_pos=cat["mask_token_pos"], vocab_columns=cols_dev)[0]
-            else:
-                scores = model(cat["input_ids"], cat["segment_ids"], cat["attention_mask"], img_feats=cat["img_feats"],
-                               mask_token_pos=cat["mask_token_pos"])[0]
+        scores = model(cat["input_ids"], cat["segment_ids"], cat["attention_mask"], img_feats=cat["img_feats"],
+                       mask_token_pos=cat["mask_token_pos"], vocab_columns=cols_dev)[0]      # (None: all V columns)
         # colour gather + per-query argmax run on the device (cpt_select_regions): only indices leave the GPU
         sets = [list(s) for q in chunk for s in q["colors"]]
         if col_of is not None:      # (ids -> positions in the column list the scores were computed for)
@@ -96,9 +130,10 @@ def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4
         first = [0]
         for q in chunk:
             first.append(first[-1] + q["input_ids"].size(0))
-        idx = scoring.select_regions_device(scores, sets, first, none_id if col_of is None else col_of[int(none_id)], few_shot=few_shot)
-        chosen[_sel(idx_local, device, bucket)] = idx
-    allc = cdist.gather_fixed(chosen, len(queries), fill=-1).cpu().tolist()
+        return (scoring.select_regions_device(scores, sets, first, none_id if col_of is None else col_of[int(none_id)], few_shot=few_shot),)
+
+    chosen, = _eval_pass(len(queries), groups_of, [((), torch.int64, -1)], step, device, bucket)
+    allc = chosen.cpu().tolist()
     out = {}
     for gi, idx in enumerate(allc):
         rects = [r for rs in queries[gi]["rects"] for r in rs]
@@ -128,19 +163,19 @@ def _apply_lr(optimizer, lr, head_multiplier):
         g["lr"] = lr
 
 
-def train_batch(model, optimizer, batches, opts, device, global_step=0):
-    """One pass over ``batches`` (dicts with img_feats, input_ids, attention_mask, segment_ids, mask_token_pos, colors): the few-shot
-    step of fewshot/refcoco_cpt.py:225-255 -- label grid, scheduled learning rate, zero_grad / forward / backward / step; a step that
-    raises RuntimeError is logged and skipped without advancing the schedule.  Returns (global_step, [loss tensors])."""
+def _scheduled_pass(model, optimizer, batches, opts, device, global_step, grid_fn):
+    """The loop train_batch and train_vg_batch share: per batch the scheduled learning rate, then zero_grad / forward with
+    masked_lm_labels=grid_fn(batch) / backward / step; a step that raises RuntimeError is logged and skipped without advancing the schedule.
+    Returns (global_step, [loss tensors])."""
     model.train()
     losses = []
     for index, host_batch in enumerate(batches):
-        batch = {name: t.to(device) for name, t in host_batch.items()}
+        batch = {name: torch.as_tensor(t).to(device) for name, t in host_batch.items()}
         _apply_lr(optimizer, get_lr_sched(global_step, opts), getattr(opts, "lr_mul", 1.0))
         try:
             optimizer.zero_grad()
             loss = model(batch["input_ids"], batch["segment_ids"], batch["attention_mask"], img_feats=batch["img_feats"],
-                         masked_lm_labels=_label_grid(batch))[0]
+                         masked_lm_labels=grid_fn(batch))[0]
             loss.backward()
             optimizer.step()
         except RuntimeError as err:
@@ -149,6 +184,13 @@ def train_batch(model, optimizer, batches, opts, device, global_step=0):
         global_step += 1
         losses.append(loss.detach())
     return global_step, losses
+
+
+def train_batch(model, optimizer, batches, opts, device, global_step=0):
+    """One pass over ``batches`` (dicts with img_feats, input_ids, attention_mask, segment_ids, mask_token_pos, colors): the few-shot
+    step of fewshot/refcoco_cpt.py:225-255 -- label grid, scheduled learning rate, zero_grad / forward / backward / step; a step that
+    raises RuntimeError is logged and skipped without advancing the schedule (_scheduled_pass).  Returns (global_step, [loss tensors])."""
+    return _scheduled_pass(model, optimizer, batches, opts, device, global_step, _label_grid)
 
 
 # ---- VG-CPT (Oscar/oscar/fewshot/vg_cpt.py; launched by cmds/vg/_fsl.sh with 16 pairs per GPU) ------------------------------------
@@ -163,11 +205,7 @@ def _vg_cat(chunk, device, per_pair, trim=False):
     if trim:
         out, li = _trim_host(out, pos)
     out = {k: v.to(device, non_blocking=True) for k, v in out.items()}
-    feats = []
-    for q in chunk:
-        f = t(q["img_feats"])[..., :li, :].to(device, non_blocking=True)
-        feats.append(f.unsqueeze(0).expand(per_pair, -1, -1) if f.dim() == 2 else f)
-    out["img_feats"] = torch.cat(feats, 0).contiguous()
+    out["img_feats"] = torch.cat([_seq_feats(q["img_feats"], per_pair, device, li) for q in chunk], 0).contiguous()
     out["mask_token_pos"] = pos.to(device)
     return out
 
@@ -180,19 +218,18 @@ def val_vg(model, pairs, idx2pred, device, batch_pairs=16, trim=False, bucket=Fa
     Returns (scores (pairs, 2, C) fp32 on the device, keys): keys[2 i] = pair i's key, keys[2 i + 1] = its reverse_imkey -- the rows of
     scores.view(-1, C), in dataset order, as scoring.vg_eval_table takes them.  trim / bucket: see the top of this module."""
     model.eval()
-    rank, world = cdist.rank_world()
-    lo, hi = cdist.shard_range(len(pairs), rank, world)
     C = max(int(i) for i in idx2pred) + 1
-    local = torch.zeros((hi - lo, 2, C), dtype=torch.float32, device=device)
-    keys = [_item_length(q["attention_mask"], np.asarray(q["input_ids"]).shape[1]) for q in pairs[lo:hi]] if bucket else None
-    for idx in _walk(hi - lo, batch_pairs, keys):
-        chunk = [pairs[lo + i] for i in idx]
-        b = _vg_cat(chunk, device, 6, trim)
-        with torch.no_grad():
-            sc = scoring.vg_predicate_scores(model, b["input_ids"], b["segment_ids"], b["attention_mask"], b["img_feats"],
-                                             b["mask_token_pos"], idx2pred)
-        local[_sel(idx, device, bucket)] = sc
-    scores = cdist.gather_fixed(local, len(pairs), fill=0)
+
+    def groups_of(lo, hi):
+        return _walk(hi - lo, batch_pairs,
+                     [_item_length(q["attention_mask"], np.asarray(q["input_ids"]).shape[1]) for q in pairs[lo:hi]] if bucket else None)
+
+    def step(idx, lo):
+        b = _vg_cat([pairs[lo + i] for i in idx], device, 6, trim)
+        return (scoring.vg_predicate_scores(model, b["input_ids"], b["segment_ids"], b["attention_mask"], b["img_feats"], b["mask_token_pos"],
+                                            idx2pred),)
+
+    scores, = _eval_pass(len(pairs), groups_of, [((2, C), torch.float32, 0)], step, device, bucket)
     keys = []
     for q in pairs:
         keys += [q["img_key"], scoring.reverse_imkey(q["img_key"])]
@@ -219,25 +256,9 @@ def train_vg_batch(model, optimizer, batches, opts, device, global_step=0):
     """One pass of vg_cpt.py:217-252 (train_batch) over ``batches``: dicts with img_feats, input_ids, attention_mask, segment_ids,
     mask_token_pos (n, 2) (sequence, position) and row_labels (n,) -- prompts.assemble_vg_train rows concatenated, 6 labelled rows per
     pair.  The label grid holds several labelled positions per sequence (the multi-row training path of REC_MLM_CPT.forward); LR
-    schedule (opts from vg_schedule), zero_grad / forward / backward / step and the skipped-step rule as train_batch.
+    schedule (opts from vg_schedule), zero_grad / forward / backward / step and the skipped-step rule as train_batch (_scheduled_pass).
     Returns (global_step, [loss tensors])."""
-    model.train()
-    losses = []
-    for index, host_batch in enumerate(batches):
-        batch = {name: torch.as_tensor(t).to(device) for name, t in host_batch.items()}
-        _apply_lr(optimizer, get_lr_sched(global_step, opts), getattr(opts, "lr_mul", 1.0))
-        try:
-            optimizer.zero_grad()
-            loss = model(batch["input_ids"], batch["segment_ids"], batch["attention_mask"], img_feats=batch["img_feats"],
-                         masked_lm_labels=vg_label_grid(batch))[0]
-            loss.backward()
-            optimizer.step()
-        except RuntimeError as err:
-            logger.info("step %d of this pass skipped: %s", index, err)
-            continue
-        global_step += 1
-        losses.append(loss.detach())
-    return global_step, losses
+    return _scheduled_pass(model, optimizer, batches, opts, device, global_step, vg_label_grid)
 
 
 # ---- VCR Q->AR (Oscar/oscar/fewshot/vcr_qar_nsp_cpt.py; launched by cmds/vcr/qar_cpt_fsl.sh) ----------------------------------------------
@@ -256,11 +277,7 @@ def _qar_blocks(chunk, device, trim=False):
         host = [batching.trim(b, lt, li) for b in host]
     blocks = []
     for part, b in zip(("q_a", "qa_r"), host):
-        feats = []
-        for q in chunk:
-            f = t(q["img_feats"])[..., :li, :].to(device, non_blocking=True)
-            n = q[part]["input_ids"].shape[0]
-            feats.append(f.unsqueeze(0).expand(n, -1, -1) if f.dim() == 2 else f)
+        feats = [_seq_feats(q["img_feats"], q[part]["input_ids"].shape[0], device, li) for q in chunk]
         blocks.append({"input_ids": b["input_ids"].to(device, non_blocking=True),
                        "attention_mask": b["attention_mask"].to(device, non_blocking=True),
                        "token_type_ids": b["segment_ids"].to(device, non_blocking=True),
@@ -284,45 +301,40 @@ def val_vcr_qar(model, questions, device, batch_questions=4, trim=False, bucket=
     trim / bucket: see the top of this module."""
     model.eval()
     n_ans, n_rats = _qar_layout(questions)
-    rank, world = cdist.rank_world()
-    lo, hi = cdist.shard_range(len(questions), rank, world)
-    preds = torch.full((hi - lo, 2), -1, dtype=torch.int64, device=device)
-    flags = torch.zeros((hi - lo, 3), dtype=torch.uint8, device=device)
-    scores = torch.zeros((hi - lo, n_ans + n_rats), dtype=torch.float32, device=device)
-    keys = None
-    if bucket:
-        keys = [max(_item_length(q[part]["input_mask"], q[part]["input_ids"].shape[1]) for part in ("q_a", "qa_r")) for q in questions[lo:hi]]
-    for idx in _walk(hi - lo, batch_questions, keys):
+
+    def groups_of(lo, hi):
+        keys = None
+        if bucket:
+            keys = [max(_item_length(q[part]["input_mask"], q[part]["input_ids"].shape[1]) for part in ("q_a", "qa_r")) for q in questions[lo:hi]]
+        return _walk(hi - lo, batch_questions, keys)
+
+    def step(idx, lo):
         chunk = [questions[lo + i] for i in idx]
         qa, qr = _qar_blocks(chunk, device, trim)
-        with torch.no_grad():
-            _, _, sc = model.qar_forward(qa, qr, return_scores=True)
+        _, _, sc = model.qar_forward(qa, qr, return_scores=True)
         nq = len(chunk)
         B0 = nq * n_ans
         p, f = scoring.vcr_qar_choose_device(sc[:B0], sc[B0:], [q["label"][0] for q in chunk], [q["label"][1] for q in chunk], n_ans, n_rats)
-        sel = _sel(idx, device, bucket)
-        preds[sel], flags[sel] = p, f
-        scores[sel] = torch.cat([sc[:B0].view(nq, n_ans), sc[B0:].view(nq, n_rats)], 1)
+        return p, f, torch.cat([sc[:B0].view(nq, n_ans), sc[B0:].view(nq, n_rats)], 1)
+
     n = len(questions)
-    preds = cdist.gather_fixed(preds, n, fill=-1).cpu()
-    flags = cdist.gather_fixed(flags, n, fill=0).cpu()
-    scores = cdist.gather_fixed(scores, n, fill=0).cpu()
+    outputs = [((2,), torch.int64, -1), ((3,), torch.uint8, 0), ((n_ans + n_rats,), torch.float32, 0)]
+    preds, flags, scores = (t.cpu() for t in _eval_pass(n, groups_of, outputs, step, device, bucket))
     q_ids = [q["q_id"] for q in questions]
-    last = {}
-    for i, qid in enumerate(q_ids):        # de-duplication by questionId: the last entry wins (vcr_qar_nsp_cpt.py:682)
-        last[qid] = i
-    keep = sorted(last.values())
-    acc = {k: float(flags[keep, j].sum().item()) / n for j, k in enumerate(("q_a", "qa_r", "q_ar"))}
+    acc = dict(zip(("q_a", "qa_r", "q_ar"), _dedup_accuracy(flags, q_ids, n)))
     return {"preds": preds, "flags": flags, "scores": scores, "q_ids": q_ids, "acc": acc}
 
 
 def qar_accumulation(n_examples, per_gpu_train_batch_size, world_size, n_batches, num_train_epochs=1, max_steps=0):
-    """vcr_qar_nsp_cpt.py:399-407: gradient_accumulation_steps = max(1, len(dataset) // (per_gpu_bs * world)) -- one optimizer step per epoch --
-    and t_total (max_steps, else len(dataloader) // gradient_accumulation_steps * num_train_epochs).  Returns (gradient_accumulation_steps,
-    t_total)."""
+    """vcr_qar_nsp_cpt.py:399-407 and gqa_cpt.py:328-334: gradient_accumulation_steps = max(1, len(dataset) // (per_gpu_bs * world)) -- one
+    optimizer step per epoch -- and t_total (max_steps, else len(dataloader) // gradient_accumulation_steps * num_train_epochs).  Returns
+    (gradient_accumulation_steps, t_total)."""
     gas = max(1, n_examples // (per_gpu_train_batch_size * world_size))
     t_total = max_steps if max_steps > 0 else n_batches // gas * num_train_epochs
     return gas, t_total
+
+
+gqa_accumulation = qar_accumulation
 
 
 def train_vcr_qar_batch(model, optimizer, scheduler, batches, opts, device, global_step=0):
@@ -330,37 +342,21 @@ def train_vcr_qar_batch(model, optimizer, scheduler, batches, opts, device, glob
     class-0 labels of both blocks (qar_choice_labels), loss = q_a_loss + qa_r_loss from ONE encoder pass (qar_forward), divided by
     opts.gradient_accumulation_steps when that is > 1, backward, torch.nn.utils.clip_grad_norm_(model.parameters(), opts.max_grad_norm) on EVERY
     micro-step (in place on the accumulated gradient, as the reference), and every gradient_accumulation_steps micro-steps scheduler.step() BEFORE
-    optimizer.step(), then model.zero_grad().  Micro-steps that do not complete a window take no optimizer step and their gradient is kept (the
-    reference zeroes only after a step).  Returns (global_step, [loss tensors, as divided])."""
+    optimizer.step(), then model.zero_grad() (_accumulate, with the host clip).  Micro-steps that do not complete a window take no optimizer step
+    and their gradient is kept (the reference zeroes only after a step).  Returns (global_step, [loss tensors, as divided])."""
     model.train()
-    gas = max(1, int(getattr(opts, "gradient_accumulation_steps", 1)))
-    max_norm = float(getattr(opts, "max_grad_norm", 1.0))
-    losses = []
-    for step, chunk in enumerate(batches):
-        n_ans, n_rats = _qar_layout(chunk)
-        qa, qr = _qar_blocks(chunk, device)
-        la, lr_ = scoring.qar_choice_labels([q["label"][0] for q in chunk], [q["label"][1] for q in chunk], n_ans, n_rats)
-        loss = model.qar_forward(qa, qr, la, lr_)[0]
-        if gas > 1:
-            loss = loss / gas
-        loss.backward()
-        torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)
-        losses.append(loss.detach())
-        if (step + 1) % gas == 0:
-            scheduler.step()
-            optimizer.step()
-            model.zero_grad()
-            global_step += 1
+
+    def micro():
+        for chunk in batches:
+            n_ans, n_rats = _qar_layout(chunk)
+            qa, qr = _qar_blocks(chunk, device)
+            la, lr_ = scoring.qar_choice_labels([q["label"][0] for q in chunk], [q["label"][1] for q in chunk], n_ans, n_rats)
+            yield model.qar_forward(qa, qr, la, lr_)[0]
+    global_step, losses, _ = _accumulate(model, optimizer, scheduler, micro(), opts, global_step, use_device_clip=False)
     return global_step, losses
 
 
 # ---- GQA-CPT (Oscar/oscar/fewshot/gqa_cpt.py; BASELINE config 4) and VCR Q->A (fewshot/vcr_nsp_cpt.py; config 5) -----------------------------
-def _seq_feats(f, n, device):
-    """img_feats (Li, D) of one question expanded to its n sequences on the device (the collate functions stack it per sequence)."""
-    f = torch.as_tensor(f).to(device, non_blocking=True)
-    return f.unsqueeze(0).expand(n, -1, -1) if f.dim() == 2 else f
-
-
 def val_gqa(model, questions, labels, tokenizer, device, batch_questions=256, trim=False, bucket=False):
     """Evaluation pass of gqa_cpt.py:558-636 (evaluate) on REC_MLM_CPT.  questions: prompts.assemble_gqa dicts with ``img_feats`` (Li, D) and
     ``igt``, the question's ground-truth label indices (eval_dic[str(q_id)]); labels: the data set's answer strings.  Questions are sharded over
@@ -376,14 +372,13 @@ def val_gqa(model, questions, labels, tokenizer, device, batch_questions=256, tr
     cols = torch.tensor(token_ids, dtype=torch.int64, device=device)
     piece = torch.tensor(piece_sid, dtype=torch.int32, device=device)
     gt_all = scoring.gqa_gt_table([q["igt"] for q in questions], label_sid)
-    rank, world = cdist.rank_world()
-    lo, hi = cdist.shard_range(len(questions), rank, world)
-    preds = torch.full((hi - lo,), -1, dtype=torch.int64, device=device)
-    correct = torch.zeros((hi - lo,), dtype=torch.uint8, device=device)
-    logits = torch.zeros((hi - lo, C), dtype=torch.float32, device=device)
     t = lambda x: torch.as_tensor(x)
-    keys = [_item_length(np.asarray(q["input_mask"])[None], np.asarray(q["input_ids"]).shape[0]) for q in questions[lo:hi]] if bucket else None
-    for idx in _walk(hi - lo, batch_questions, keys):
+
+    def groups_of(lo, hi):
+        return _walk(hi - lo, batch_questions, [_item_length(np.asarray(q["input_mask"])[None], np.asarray(q["input_ids"]).shape[0])
+                                                for q in questions[lo:hi]] if bucket else None)
+
+    def step(idx, lo):
         chunk = [questions[lo + i] for i in idx]
         b = {"input_ids": torch.stack([t(q["input_ids"]) for q in chunk]), "segment_ids": torch.stack([t(q["segment_ids"]) for q in chunk]),
              "attention_mask": torch.stack([t(q["input_mask"]) for q in chunk]), "img_feats": torch.stack([t(q["img_feats"]) for q in chunk])}
@@ -393,20 +388,15 @@ def val_gqa(model, questions, labels, tokenizer, device, batch_questions=256, tr
         ids, seg, msk = (b[k].to(device, non_blocking=True) for k in ("input_ids", "segment_ids", "attention_mask"))
         feats = b["img_feats"].to(device, non_blocking=True).float()
         mpos = mpos.to(device, non_blocking=True)
-        with torch.no_grad():
-            sc = model(ids, seg, msk, img_feats=feats, mask_token_pos=mpos, vocab_columns=cols)[0]
+        sc = model(ids, seg, msk, img_feats=feats, mask_token_pos=mpos, vocab_columns=cols)[0]
         p, c = scoring.gqa_choose_device(sc, piece, gt_all[torch.as_tensor(idx) + lo])
-        sel = _sel(idx, device, bucket)
-        preds[sel], correct[sel], logits[sel] = p, c, sc
+        return p, c, sc
+
     n = len(questions)
-    preds = cdist.gather_fixed(preds, n, fill=-1).cpu()
-    correct = cdist.gather_fixed(correct, n, fill=0).cpu()
-    logits = cdist.gather_fixed(logits, n, fill=0).cpu()
+    outputs = [((), torch.int64, -1), ((), torch.uint8, 0), ((C,), torch.float32, 0)]
+    preds, correct, logits = (r.cpu() for r in _eval_pass(n, groups_of, outputs, step, device, bucket))
     q_ids = [int(t(q["q_id"]).reshape(-1)[0]) for q in questions]
-    last = {}
-    for i, qid in enumerate(q_ids):        # results_dic = {k["question_id"]: k ...}: the last entry wins (gqa_cpt.py:619)
-        last[qid] = i
-    acc = float(correct[sorted(last.values())].sum().item()) / n
+    acc = _dedup_accuracy(correct, q_ids, n)
     return {"preds": preds, "answers": [answer_labels[int(p)] for p in preds.tolist()], "correct": correct, "logits": logits, "q_ids": q_ids,
             "acc": acc}
 
@@ -425,14 +415,6 @@ def gqa_label_grid(input_ids, attention_mask, label_id, label_token_ids):
     return grid
 
 
-def gqa_accumulation(n_examples, per_gpu_train_batch_size, world_size, n_batches, num_train_epochs=1, max_steps=0):
-    """gqa_cpt.py:328-334: gradient_accumulation_steps = max(1, len(dataset) // (per_gpu_bs * world)) and t_total (max_steps, else
-    len(dataloader) // gradient_accumulation_steps * num_train_epochs).  Returns (gradient_accumulation_steps, t_total)."""
-    gas = max(n_examples // (per_gpu_train_batch_size * world_size), 1)
-    t_total = max_steps if max_steps > 0 else n_batches // gas * num_train_epochs
-    return gas, t_total
-
-
 def set_dropout(model, p):
     """The adjust_dp switch of gqa_cpt.py:403-412 (0.3 from epoch 3 on): the reference sets ``p`` of model.dropout, model.bert.dropout and
     model.bert.embeddings.dropout.  Here the training step draws its masks from config.hidden_dropout_prob (train.dropout_for), one rate for
@@ -445,7 +427,8 @@ def set_dropout(model, p):
 
 
 def _accumulate(model, optimizer, scheduler, micro_losses, opts, global_step, use_device_clip=None):
-    """The accumulation loop both drivers share (gqa_cpt.py:445-462, vcr_nsp_cpt.py:452-473).  micro_losses yields one loss per micro-step; it is
+    """The accumulation loop of train_gqa_batch, train_vcr_batch and train_vcr_qar_batch (gqa_cpt.py:445-462, vcr_nsp_cpt.py:452-473,
+    vcr_qar_nsp_cpt.py:453-525).  micro_losses yields one loss per micro-step; it is
     divided by gradient_accumulation_steps when that is > 1, backward and the global-norm clip run on EVERY micro-step (in place on the
     accumulated gradient), and every gradient_accumulation_steps micro-steps scheduler.step() runs BEFORE optimizer.step(), then
     model.zero_grad().  The clip is optimizer.clip_grad_norm_device (no host synchronisation) when the optimizer has it -- use_device_clip=False
@@ -508,7 +491,7 @@ def _vcr_block(chunk, device, trim=False):
     return {"input_ids": b["input_ids"].to(device, non_blocking=True),
             "attention_mask": b["attention_mask"].to(device, non_blocking=True),
             "token_type_ids": b["segment_ids"].to(device, non_blocking=True),
-            "img_feats": torch.cat([_seq_feats(t(q["img_feats"])[..., :li, :], interval, device) for q in chunk], 0).float().contiguous()}, interval
+            "img_feats": torch.cat([_seq_feats(q["img_feats"], interval, device, li) for q in chunk], 0).float().contiguous()}, interval
 
 
 def _vcr_label(q):
@@ -525,31 +508,24 @@ def val_vcr(model, questions, device, batch_questions=8, trim=False, bucket=Fals
     trim / bucket: see the top of this module."""
     model.eval()
     interval = questions[0]["input_ids"].shape[0]
-    rank, world = cdist.rank_world()
-    lo, hi = cdist.shard_range(len(questions), rank, world)
-    preds = torch.full((hi - lo,), -1, dtype=torch.int64, device=device)
-    correct = torch.zeros((hi - lo,), dtype=torch.uint8, device=device)
-    scores = torch.zeros((hi - lo, interval), dtype=torch.float32, device=device)
-    keys = [_item_length(q["input_mask"], q["input_ids"].shape[1]) for q in questions[lo:hi]] if bucket else None
-    for idx in _walk(hi - lo, batch_questions, keys):
+
+    def groups_of(lo, hi):
+        return _walk(hi - lo, batch_questions, [_item_length(q["input_mask"], q["input_ids"].shape[1]) for q in questions[lo:hi]] if bucket else None)
+
+    def step(idx, lo):
         chunk = [questions[lo + i] for i in idx]
         b, iv = _vcr_block(chunk, device, trim)
         if iv != interval:
             raise ValueError("VCR Q->A: every question of a pass needs the same number of answer choices")
-        with torch.no_grad():
-            rel = model(b["input_ids"], b["token_type_ids"], b["attention_mask"], img_feats=b["img_feats"])[0]
+        rel = model(b["input_ids"], b["token_type_ids"], b["attention_mask"], img_feats=b["img_feats"])[0]
         sc, p, c = scoring.nsp_choose_device(rel, interval, [_vcr_label(q) for q in chunk])
-        sel = _sel(idx, device, bucket)
-        preds[sel], correct[sel], scores[sel] = p, c, sc.view(len(chunk), interval)
+        return p, c, sc.view(len(chunk), interval)
+
     n = len(questions)
-    preds = cdist.gather_fixed(preds, n, fill=-1).cpu()
-    correct = cdist.gather_fixed(correct, n, fill=0).cpu()
-    scores = cdist.gather_fixed(scores, n, fill=0).cpu()
+    outputs = [((), torch.int64, -1), ((), torch.uint8, 0), ((interval,), torch.float32, 0)]
+    preds, correct, scores = (t.cpu() for t in _eval_pass(n, groups_of, outputs, step, device, bucket))
     q_ids = [int(q["q_id"]) for q in questions]
-    last = {}
-    for i, qid in enumerate(q_ids):        # results_dic = {k["questionId"]: k ...}: the last entry wins (vcr_nsp_cpt.py:619)
-        last[qid] = i
-    acc = float(correct[sorted(last.values())].sum().item()) / n
+    acc = _dedup_accuracy(correct, q_ids, n)
     return {"preds": preds, "correct": correct, "scores": scores, "q_ids": q_ids, "acc": acc}
 
 

@@ -467,10 +467,7 @@ class PackedModel(object):
             dl = torch.empty((B, n_rel), device=dev, dtype=torch.float32)
             loss2 = torch.empty(3, device=dev, dtype=torch.float32)
             need = L.lib().cpt_rel2_workspace_bytes(B)
-            ws = self._ws.get("rel2")
-            if ws is None or ws.numel() < need or ws.device != dev:
-                ws = torch.zeros(need, device=dev, dtype=torch.uint8)      # (the finish ticket must start at 0; every call leaves it 0)
-                self._ws["rel2"] = ws
+            ws = self._buffer("rel2", need, zero=True)      # (the finish ticket must start at 0; every call leaves it 0)
             wsz = ws.numel()
             if labels_host is not None:
                 labels_host = labels_host.astype("int64", copy=False)
@@ -485,16 +482,22 @@ class PackedModel(object):
         return res
 
     # ---- forward -------------------------------------------------------------------------
+    def _buffer(self, key, need, zero=False, dtype=torch.uint8, device=None):
+        """Grow-only cache of device buffers: the one kept under ``key`` while it is on the device (default: the parameters') and holds at
+        least ``need`` elements, else a new one of ``need`` elements -- zeroed when ``zero`` is set, uninitialised otherwise."""
+        dev = self.flat.device if device is None else device
+        buf = self._ws.get(key)
+        if buf is None or buf.numel() < need or buf.device != dev:
+            buf = (torch.zeros if zero else torch.empty)(need, device=dev, dtype=dtype)
+            self._ws[key] = buf
+        return buf
+
     def workspace(self, B, Lt, Li, flags):
         m, _ = self.descriptor()
         need = L.lib().cpt_fwd_workspace_bytes(C.byref(m.dims), B, Lt, Li, flags)
         if need == 0:
             raise RuntimeError("cpt_amd: cpt_fwd_workspace_bytes rejected B=%d Lt=%d Li=%d" % (B, Lt, Li))
-        ws = self._ws.get("fwd")
-        if ws is None or ws.numel() < need or ws.device != self.flat.device:
-            ws = torch.empty(need, device=self.flat.device, dtype=torch.uint8)
-            self._ws["fwd"] = ws
-        return ws
+        return self._buffer("fwd", need)
 
     def _trim_batch(self, input_ids, token_type_ids, attention_mask, position_ids, img_feats, head_pos):
         """trim=True on a padded device batch with a 2-D mask: cut the batch to the part some sequence attends to (include/cpt_hip.h
@@ -505,10 +508,7 @@ class PackedModel(object):
         Li = img_feats.size(1) if img_feats is not None else 0
         dev = input_ids.device
         st = L.stream_ptr()
-        ext = self._ws.get("ext")
-        if ext is None or ext.device != dev:
-            ext = torch.zeros(2, device=dev, dtype=torch.int32)
-            self._ws["ext"] = ext
+        ext = self._buffer("ext", 2, zero=True, dtype=torch.int32, device=dev)
         L.check(L.lib().cpt_batch_extents(attention_mask.data_ptr(), B, Lt, Li, L.ptr(head_pos), head_pos.numel() if head_pos is not None else 0,
                                           ext.data_ptr(), st), "cpt_batch_extents")
         lt2, li2 = ext.tolist()
@@ -523,6 +523,50 @@ class PackedModel(object):
                                        L.ptr(pos2), mask2.data_ptr(), L.ptr(feats2), st), "cpt_trim_batch")
         return ids2, tt2, mask2, pos2, feats2
 
+    @staticmethod
+    def _prep(t, dt, name):
+        """An input as the C ABI reads it: on the GPU, of dtype ``dt``, contiguous (None stays None)."""
+        if t is None:
+            return None
+        if not t.is_cuda:
+            raise RuntimeError("cpt_amd: %s is on %s; inputs must be on the GPU" % (name, t.device))
+        if t.dtype != dt:
+            t = t.to(dt)
+        return t.contiguous()
+
+    def _inputs(self, input_ids, token_type_ids, attention_mask, position_ids, img_feats):
+        """What forward and forward_rows do before they differ: the weights made ready for this compute mode, the five common inputs prepared
+        (_prep) and checked against each other.  Returns ((input_ids, token_type_ids, attention_mask, position_ids, img_feats), B, Lt, Li,
+        mask3)."""
+        self.ensure_packed()
+        self.refresh_shadow()
+        if self.dtype == "bf16" and self.fold_ln:
+            self.ensure_fold()
+        prep = self._prep
+        input_ids = prep(input_ids, torch.int64, "input_ids")
+        token_type_ids = prep(token_type_ids, torch.int64, "token_type_ids")
+        position_ids = prep(position_ids, torch.int64, "position_ids")
+        mask3 = attention_mask is not None and attention_mask.dim() == 3
+        if attention_mask is not None and attention_mask.dim() not in (2, 3):
+            raise NotImplementedError("cpt_amd: attention_mask must be 2-D or 3-D (modeling_bert.py:213-218)")
+        attention_mask = prep(attention_mask, torch.int64, "attention_mask")
+        img_feats = prep(img_feats, torch.float32, "img_feats")
+        B, Lt = input_ids.shape
+        Li = img_feats.size(1) if img_feats is not None else 0
+        Lseq = Lt + Li
+        if img_feats is not None and img_feats.size(2) != self.cfg.img_feature_dim:
+            raise RuntimeError("cpt_amd: img_feats last dim %d != config.img_feature_dim %d"
+                               % (img_feats.size(2), self.cfg.img_feature_dim))
+        want = (B, Lseq, Lseq) if mask3 else (B, Lseq)
+        if attention_mask is not None and tuple(attention_mask.shape) != want:
+            raise RuntimeError("cpt_amd: attention_mask shape %s != %s" % (tuple(attention_mask.shape), want))
+        return (input_ids, token_type_ids, attention_mask, position_ids, img_feats), B, Lt, Li, mask3
+
+    def _trimmed(self, x, head_pos):
+        """_trim_batch on the five inputs of _inputs -> (the five, Lt', Li')."""
+        x = self._trim_batch(*x, head_pos)
+        return x, x[0].size(1), x[4].size(1) if x[4] is not None else 0
+
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, position_ids=None, img_feats=None,
                 mask_pos=None, labels=None, flags=0, logit_cols=None, trim=False):
         """Returns dict with the outputs selected by `flags` (see _lib.OUT_*).
@@ -533,47 +577,17 @@ class PackedModel(object):
         in list order -- the decoder then reads len(logit_cols) rows of its table instead of streaming it (cpt_outputs.logit_cols)."""
         if self.head == "qar" and flags & L.OUT_REL:
             raise RuntimeError("cpt_amd: the VCR Q->AR model has two relation heads: score them with forward_rel2 (cpt_rel2_scores), not OUT_REL")
-        self.ensure_packed()
-        self.refresh_shadow()
-        if self.dtype == "bf16" and self.fold_ln:
-            self.ensure_fold()
+        x, B, Lt, Li, mask3 = self._inputs(input_ids, token_type_ids, attention_mask, position_ids, img_feats)
         dev = self.flat.device
-
-        def prep(t, dt, name):
-            if t is None:
-                return None
-            if not t.is_cuda:
-                raise RuntimeError("cpt_amd: %s is on %s; inputs must be on the GPU" % (name, t.device))
-            if t.dtype != dt:
-                t = t.to(dt)
-            return t.contiguous()
-
-        input_ids = prep(input_ids, torch.int64, "input_ids")
-        token_type_ids = prep(token_type_ids, torch.int64, "token_type_ids")
-        position_ids = prep(position_ids, torch.int64, "position_ids")
-        mask3 = attention_mask is not None and attention_mask.dim() == 3
-        if attention_mask is not None and attention_mask.dim() not in (2, 3):
-            raise NotImplementedError("cpt_amd: attention_mask must be 2-D or 3-D (modeling_bert.py:213-218)")
-        attention_mask = prep(attention_mask, torch.int64, "attention_mask")
-        img_feats = prep(img_feats, torch.float32, "img_feats")
+        prep = self._prep
         mask_pos = prep(mask_pos, torch.int64, "mask_token_pos")
         labels = prep(labels, torch.int64, "labels")
-        B, Lt = input_ids.shape
-        Li = img_feats.size(1) if img_feats is not None else 0
         Lseq = Lt + Li
-        if img_feats is not None and img_feats.size(2) != self.cfg.img_feature_dim:
-            raise RuntimeError("cpt_amd: img_feats last dim %d != config.img_feature_dim %d"
-                               % (img_feats.size(2), self.cfg.img_feature_dim))
-        want = (B, Lseq, Lseq) if mask3 else (B, Lseq)
-        if attention_mask is not None and tuple(attention_mask.shape) != want:
-            raise RuntimeError("cpt_amd: attention_mask shape %s != %s" % (tuple(attention_mask.shape), want))
         call_flags = flags | (L.ATTN_MASK_3D if mask3 else 0)      # (B, L, L): one mask row per query (modeling_bert.py:215-216)
         if (trim and attention_mask is not None and not mask3 and labels is None and not flags & (L.OUT_SEQ | L.OUT_ALL_LOGITS | L.OUT_LOSS)
                 and (mask_pos is not None or not flags & L.OUT_MASK_LOGITS)):
-            input_ids, token_type_ids, attention_mask, position_ids, img_feats = self._trim_batch(
-                input_ids, token_type_ids, attention_mask, position_ids, img_feats, mask_pos if flags & L.OUT_MASK_LOGITS else None)
-            Lt = input_ids.size(1)
-            Li = img_feats.size(1) if img_feats is not None else 0
+            x, Lt, Li = self._trimmed(x, mask_pos if flags & L.OUT_MASK_LOGITS else None)
+        input_ids, token_type_ids, attention_mask, position_ids, img_feats = x
         self.last_shape = (B, Lt, Li)
         m, _ = self.descriptor()
         H, V = self.cfg.hidden_size, self.cfg.vocab_size
@@ -623,47 +637,18 @@ class PackedModel(object):
         (row_seq ascending, any number of rows per sequence).  Returns {"logits": (n, len(cols)) -- or (n, V) without cols --,
         "lse": (n,) natural-log log-sum-exp of each row over all V columns (None with lse=False)}.
         trim: as in ``forward`` (skipped with a 3-D mask or without a mask)."""
-        self.ensure_packed()
-        self.refresh_shadow()
-        if self.dtype == "bf16" and self.fold_ln:
-            self.ensure_fold()
-        dev = self.flat.device
-
-        def prep(t, dt, name):
-            if t is None:
-                return None
-            if not t.is_cuda:
-                raise RuntimeError("cpt_amd: %s is on %s; inputs must be on the GPU" % (name, t.device))
-            return t.to(dt).contiguous()
-
         if row_seq is None or mask_pos is None:
             raise RuntimeError("cpt_amd: forward_rows needs row_seq and mask_pos")
-        input_ids = prep(input_ids, torch.int64, "input_ids")
-        token_type_ids = prep(token_type_ids, torch.int64, "token_type_ids")
-        position_ids = prep(position_ids, torch.int64, "position_ids")
-        mask3 = attention_mask is not None and attention_mask.dim() == 3
-        if attention_mask is not None and attention_mask.dim() not in (2, 3):
-            raise NotImplementedError("cpt_amd: attention_mask must be 2-D or 3-D (modeling_bert.py:213-218)")
-        attention_mask = prep(attention_mask, torch.int64, "attention_mask")
-        img_feats = prep(img_feats, torch.float32, "img_feats")
+        x, B, Lt, Li, mask3 = self._inputs(input_ids, token_type_ids, attention_mask, position_ids, img_feats)
+        dev = self.flat.device
+        prep = self._prep
         row_seq = prep(row_seq.reshape(-1), torch.int64, "row_seq")
         mask_pos = prep(mask_pos.reshape(-1), torch.int64, "mask_pos")
         if row_seq.numel() != mask_pos.numel():
             raise RuntimeError("cpt_amd: row_seq has %d entries, mask_pos %d" % (row_seq.numel(), mask_pos.numel()))
-        B, Lt = input_ids.shape
-        Li = img_feats.size(1) if img_feats is not None else 0
-        Lseq = Lt + Li
-        if img_feats is not None and img_feats.size(2) != self.cfg.img_feature_dim:
-            raise RuntimeError("cpt_amd: img_feats last dim %d != config.img_feature_dim %d"
-                               % (img_feats.size(2), self.cfg.img_feature_dim))
-        want = (B, Lseq, Lseq) if mask3 else (B, Lseq)
-        if attention_mask is not None and tuple(attention_mask.shape) != want:
-            raise RuntimeError("cpt_amd: attention_mask shape %s != %s" % (tuple(attention_mask.shape), want))
         if trim and attention_mask is not None and not mask3:
-            input_ids, token_type_ids, attention_mask, position_ids, img_feats = self._trim_batch(
-                input_ids, token_type_ids, attention_mask, position_ids, img_feats, mask_pos)
-            Lt = input_ids.size(1)
-            Li = img_feats.size(1) if img_feats is not None else 0
+            x, Lt, Li = self._trimmed(x, mask_pos)
+        input_ids, token_type_ids, attention_mask, position_ids, img_feats = x
         self.last_shape = (B, Lt, Li)
         V = self.cfg.vocab_size
         n = row_seq.numel()
@@ -677,10 +662,7 @@ class PackedModel(object):
                      position_ids=L.ptr(position_ids), attn_mask=L.ptr(attention_mask), img_feats=L.ptr(img_feats),
                      mask_pos=mask_pos.data_ptr(), labels=None, n_rows=n, mask_3d=1 if mask3 else 0, row_seq=row_seq.data_ptr())
         need = L.lib().cpt_fwd_rows_workspace_bytes(C.byref(m.dims), B, Lt, Li, n, nc) if n > 0 else 0
-        ws = self._ws.get("rows")
-        if need and (ws is None or ws.numel() < need or ws.device != dev):
-            ws = torch.empty(need, device=dev, dtype=torch.uint8)
-            self._ws["rows"] = ws
+        ws = self._buffer("rows", need) if need else self._ws.get("rows")
         L.check(L.lib().cpt_model_fwd_rows(C.byref(m), C.byref(bt), L.ptr(cols), nc, out["logits"].data_ptr(), L.ptr(out["lse"]),
                                            L.ptr(ws), ws.numel() if ws is not None else 0, L.stream_ptr()), "cpt_model_fwd_rows")
         return out
