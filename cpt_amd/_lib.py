@@ -73,6 +73,11 @@ class Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("seq", "pooled", "logits", "loss", "rel", "loss_mean", "logit_cols")] + [("n_logit_cols", C.c_int64)]
 
 
+class SoftTemplate(C.Structure):
+    """cpt_soft_template: the trainable prompt rows that replace the word rows of ids 1 .. n_slots - 1 (cpt_amd/soft_prompt.py)."""
+    _fields_ = [("tmpl", C.c_void_p), ("g_tmpl", C.c_void_p), ("n_slots", C.c_int)]
+
+
 class Rel2(C.Structure):
     """cpt_rel2: the second relation head of VCR Q->AR (rows [B0, B) of the batch)."""
     _fields_ = [("B0", C.c_int32)] + [(n, C.c_void_p) for n in ("w_rel1", "b_rel1", "g_w_rel1", "g_b_rel1", "score", "labels_host")]
@@ -103,6 +108,11 @@ _SIGS = {
     "cpt_train_bwd_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(Batch), C.POINTER(ModelGrads), C.c_float, vp, vp, C.c_size_t, vp,
                                      BUCKET_CB, vp, C.POINTER(Dropout)]),
     "cpt_train_zero_grads_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(ModelGrads), C.c_int, vp]),
+    "cpt_model_fwd_soft": (C.c_int, [C.POINTER(Model), C.POINTER(SoftTemplate), C.POINTER(Batch), C.POINTER(Outputs), C.c_int, vp, C.c_size_t, vp]),
+    "cpt_model_fwd_rows_soft": (C.c_int, [C.POINTER(Model), C.POINTER(SoftTemplate), C.POINTER(Batch), vp, C.c_int, vp, vp, vp, C.c_size_t, vp]),
+    "cpt_train_fwd_soft": (C.c_int, [C.POINTER(Model), C.POINTER(SoftTemplate), C.POINTER(Batch), C.POINTER(Outputs), vp, C.c_size_t, vp, BUCKET_CB, vp,
+                                     C.POINTER(Dropout)]),
+    "cpt_train_bwd_soft": (C.c_int, [C.POINTER(Model), C.POINTER(SoftTemplate), C.POINTER(Batch), C.c_float, vp, vp, C.c_size_t, vp, C.POINTER(Dropout)]),
     "cpt_train_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int, C.c_int]),
     "cpt_train_workspace_bytes_rows": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int, C.c_int, C.c_int]),
     "cpt_train_fwd": (C.c_int, [C.POINTER(Model), C.POINTER(Batch), C.POINTER(Outputs), vp, C.c_size_t, vp]),

@@ -243,7 +243,7 @@ int col_jobs_flush(const ColJobs& jobs, hipStream_t s) {
     return CPT_OK;
 }
 
-template <typename LP, bool GELU_IN, int NA = 4>      // NA: float4 per lane per row array (4: any H <= 1024; 3: the H = 768 instantiation -- a quarter fewer registers, 36 instead of 48 KB of staging: four workgroups per CU)
+template <typename LP, bool GELU_IN, int NA = 4, bool SUMS = true>      // SUMS false (frozen model, LnBwdExtra::no_sums): no column sums are formed or written;   NA: float4 per lane per row array (4: any H <= 1024; 3: the H = 768 instantiation -- a quarter fewer registers, 36 instead of 48 KB of staging: four workgroups per CU)
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                      const float* __restrict__ g, float eps, float* dx,      // (dx may be dy_resid's buffer: every row is read before it is written)
                                                      LP* __restrict__ dx_lp, float* __restrict__ dg, float* __restrict__ db,
@@ -396,8 +396,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
                     const float gy = dv[i][j] * gg[i][j];
                     s1 += gy;
                     s2 += gy * xh;
+                    if constexpr (SUMS) {
                     gsum[i][j] += dv[i][j] * xh;
                     bsum[i][j] += dv[i][j];
+                    }
                 }
             }
         s1 = wave_sum(s1) / (float)H;
@@ -425,7 +427,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
 #pragma unroll
                     for (int j = 0; j < 4; ++j) o[j] = keep[j] ? o[j] * dr.scale : 0.f;
                 }
-                if (dbias) {
+                if (SUMS && dbias) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) xsum[i][j] += o[j];
                 }
@@ -442,6 +444,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
             }
         }
     }
+    if constexpr (!SUMS) return;
     // reduce dg/db over the 4 waves, one atomic per column per workgroup  (one pass over a [3][4][H] staging array: the 16 KB
     // one-sum-at-a-time form that lets eight workgroups share a CU was measured SLOWER, 19.5 vs 16.8 us at 3840 rows -- the kernel
     // is bound by its per-row dependency chain, not by occupancy)
@@ -496,27 +499,33 @@ int ln_bwd(const float* dy, const float* x, const float* g, float eps, float* dx
     if ((dr.thresh != 0 && (!g || grp != R)) || (dbias && !g)) return CPT_ERR_SHAPE;      // mask: compact rows only (its element index is the compact row's); bias sums: any row placement, but not the plain row gather
     const int nsum = dbias ? 3 : 2;
     if (R <= 0 || H % 4 || H > 256 * LNB_MAXV || grp <= 0) return CPT_ERR_SHAPE;
-    if (!dy || (g && (!x || !dg || !db))) return CPT_ERR_NULL;      // g == NULL: identity (row gather only)
     const LnBwdExtra e0 = {};
     const LnBwdExtra& ex = ext ? *ext : e0;
+    const bool sums = !ex.no_sums;
+    if (!dy || (g && (!x || (sums && (!dg || !db))))) return CPT_ERR_NULL;      // g == NULL: identity (row gather only)
+    if (!sums && (!g || dbias || ex.defer_reduce || ex.jobs)) return CPT_ERR_SHAPE;      // no column sums: nothing to sum into, to leave behind or to carry
     if (ex.dy_parts > 1 && (grp != R || !g)) return CPT_ERR_SHAPE;
     if (ex.dy_parts_bf16 && ex.dy_parts != 2) return CPT_ERR_SHAPE;
     if (ex.defer_reduce && !(g && part && (size_t)ln_bwd_part_rows(R) * nsum * H * 4 <= part_bytes)) return CPT_ERR_WORKSPACE;
     // rows per block: with atomics fewer blocks = fewer dgamma/dbeta atomics (2*H per block); with a partial-sum buffer (two-stage
     // column sums) one row per wave keeps 4x the rows in flight: the kernel is latency-bound otherwise (22 -> ~10 us at 3840 rows)
     int rpb = R >= 2048 ? 16 : (R > 256 ? 8 : 4);      // (a few rows -- the head's 4 .. 64 -- one per wave: each wave's row chain once instead of twice in sequence)
-    if (g && part && (R >= 1024 || ex.defer_reduce) && (size_t)ln_bwd_part_rows(R) * nsum * H * 4 <= part_bytes) rpb = ln_bwd_rpb_two_stage(R); else part = nullptr;      // 8: two rows per wave, half the partial rows (3840 rows: 5.83 vs 5.89 ms per step; 960 blocks of 4 rows are 1.25 rounds of the 3 blocks per CU the 48 KB staging array allows)
+    if (g && part && (R >= 1024 || ex.defer_reduce) && (size_t)ln_bwd_part_rows(R) * nsum * H * 4 <= part_bytes) rpb = ln_bwd_rpb_two_stage(R); else part = nullptr;
+    if (!sums) { part = nullptr; rpb = ln_bwd_rpb_two_stage(R); }      // (no atomics to save on: the two-stage form's rows per workgroup)      // 8: two rows per wave, half the partial rows (3840 rows: 5.83 vs 5.89 ms per step; 960 blocks of 4 rows are 1.25 rounds of the 3 blocks per CU the 48 KB staging array allows)
     const int nb = (R + rpb - 1) / rpb;
     const ColJobs j0 = {};
     const ColJobs& jobs = ex.jobs ? *ex.jobs : j0;
     dim3 grid(nb + col_jobs_blocks(&jobs)), block(256);
     const bool lp16 = dx_lp && lp_dtype == CPT_BF16;
     const int dyp = ex.dy_parts > 1 ? ex.dy_parts : 1;
-#define LNB(LPT, GI) do { if (H == 768) ln_bwd_kernel<LPT, GI, 3><<<grid, block, 0, s>>>(dy, x, g, eps, dx, (LPT*)dx_lp, dg, db, R, H, grp, grp_stride, grp_off, rpb, part, dr, dbias, ex.stats, dyp, ex.dy_stride, ex.dy_resid, (ex.dy_parts_bf16 && dyp == 2) ? 1 : 0, nb, jobs, ex.drop_rows, (dr.thresh != 0 && H <= 1024) ? ex.keep_bits : nullptr, ex.in_drop); \
-                          else ln_bwd_kernel<LPT, GI, 4><<<grid, block, 0, s>>>(dy, x, g, eps, dx, (LPT*)dx_lp, dg, db, R, H, grp, grp_stride, grp_off, rpb, part, dr, dbias, ex.stats, dyp, ex.dy_stride, ex.dy_resid, (ex.dy_parts_bf16 && dyp == 2) ? 1 : 0, nb, jobs, ex.drop_rows, (dr.thresh != 0 && H <= 1024) ? ex.keep_bits : nullptr, ex.in_drop); } while (0)
+#define LNB_ARGS(LPT) dy, x, g, eps, dx, (LPT*)dx_lp, dg, db, R, H, grp, grp_stride, grp_off, rpb, part, dr, dbias, ex.stats, dyp, ex.dy_stride, ex.dy_resid, (ex.dy_parts_bf16 && dyp == 2) ? 1 : 0, nb, jobs, ex.drop_rows, (dr.thresh != 0 && H <= 1024) ? ex.keep_bits : nullptr, ex.in_drop
+#define LNB(LPT, GI) do { if (!sums) { if (H == 768) ln_bwd_kernel<LPT, GI, 3, false><<<grid, block, 0, s>>>(LNB_ARGS(LPT)); else ln_bwd_kernel<LPT, GI, 4, false><<<grid, block, 0, s>>>(LNB_ARGS(LPT)); } \
+                          else if (H == 768) ln_bwd_kernel<LPT, GI, 3><<<grid, block, 0, s>>>(LNB_ARGS(LPT)); \
+                          else ln_bwd_kernel<LPT, GI, 4><<<grid, block, 0, s>>>(LNB_ARGS(LPT)); } while (0)
     if (lp16) { if (gelu_in) LNB(bf16, true); else LNB(bf16, false); }
     else      { if (gelu_in) LNB(float, true); else LNB(float, false); }
 #undef LNB
+#undef LNB_ARGS
     if (part && !ex.defer_reduce) {
         const int per = 16;
         ln_bwd_reduce_kernel<<<dim3((nsum * H + 255) / 256, (nb + per - 1) / per), dim3(256), 0, s>>>(part, dg, db, dbias, nb, H, per);
@@ -698,6 +707,114 @@ int embed_bwd(const float* dy, const int64_t* ids, const int64_t* tt, const int6
     dim3 grid((B * Lt + rpb - 1) / rpb), block(256);
     embed_bwd_kernel<<<grid, block, 0, s>>>(dy, ids, tt, pos, word, posw, typew, g, eps, dword, dposw, dtypew, dg, db,
                                            B, Lt, L, H, vocab, max_pos, type_vocab, rpb, in_drop ? *in_drop : DropSpec{});
+    return CPT_OK;
+}
+
+// ---- soft template: embedding LayerNorm backward on the slot rows, summed per slot -----------------------
+// One workgroup per slot (cpt_hip.h cpt_soft_template): every wave scans the B * Lt ids in row order (64 per step, one ballot), the k-th
+// row that holds the slot goes to wave k % 4, which runs the row's LayerNorm backward (the arithmetic of embed_bwd_kernel, the word row
+// taken from the template) and adds the word-row gradient to its registers; the four waves' sums are then added in wave order.  Every
+// term has a fixed place in a fixed association: no atomics, the same inputs give the same bits.  dtmpl is written whole: slot 0 and
+// slots no row uses receive zeros.  Nothing else is written.
+__global__ __launch_bounds__(256) void soft_template_bwd_kernel(
+    const float* __restrict__ dy, const int64_t* __restrict__ ids, const int64_t* __restrict__ tt, const int64_t* __restrict__ pos,
+    const float* __restrict__ tmpl, const float* __restrict__ posw, const float* __restrict__ typew, const float* __restrict__ g,
+    float eps, float* __restrict__ dtmpl, int B, int Lt, int L, int H, int max_pos, int type_vocab, DropSpec idr) {
+    __shared__ float red[4][256 * LNB_MAXV];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int slot = blockIdx.x;
+    const int nv = (H + 255) / 256;
+    const int R = B * Lt;
+    f32x4 acc[LNB_MAXV], gg[LNB_MAXV];
+#pragma unroll
+    for (int i = 0; i < LNB_MAXV; ++i) {
+        acc[i] = f32x4{0, 0, 0, 0};
+        const int c = (lane + 64 * i) * 4;
+        gg[i] = (i < nv && c < H) ? *reinterpret_cast<const f32x4*>(g + c) : f32x4{0, 0, 0, 0};
+    }
+    int seen = 0;      // rows of this slot met so far (wave-uniform)
+    for (int r0 = 0; slot > 0 && r0 < R; r0 += 64) {
+        const bool mine = r0 + lane < R && ids[r0 + lane] == (int64_t)slot;
+        unsigned long long hits = __ballot(mine);
+        while (hits) {
+            const int k = __ffsll((long long)hits) - 1;
+            hits &= hits - 1;
+            const int turn = seen++ & 3;
+            if (turn != wave) continue;
+            const int r = r0 + k, b = r / Lt, t = r % Lt;
+            long pid = pos ? pos[r] : t, tid = tt ? tt[r] : 0;
+            pid = pid < 0 ? 0 : (pid >= max_pos ? max_pos - 1 : pid);
+            tid = tid < 0 ? 0 : (tid >= type_vocab ? type_vocab - 1 : tid);
+            f32x4 xv[LNB_MAXV], dv[LNB_MAXV];
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < LNB_MAXV; ++i) {
+                const int c = (lane + 64 * i) * 4;
+                if (i < nv && c < H) {
+                    const f32x4 a = *reinterpret_cast<const f32x4*>(tmpl + (size_t)slot * H + c);
+                    const f32x4 p = *reinterpret_cast<const f32x4*>(posw + (size_t)pid * H + c);
+                    const f32x4 q = *reinterpret_cast<const f32x4*>(typew + (size_t)tid * H + c);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) xv[i][j] = a[j] + p[j] + q[j];
+                    dv[i] = *reinterpret_cast<const f32x4*>(dy + ((size_t)b * L + t) * H + c);
+                    if (idr.thresh != 0) {      // BertEmbeddings' dropout, backward: the mask of the forward at the same element index
+                        bool keep[4];
+                        drop_hidden4(idr, (((uint64_t)b * L + t) * H + c) >> 2, keep);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) dv[i][j] = keep[j] ? dv[i][j] * idr.scale : 0.f;
+                    }
+                    s += xv[i][0] + xv[i][1] + xv[i][2] + xv[i][3];
+                }
+            }
+            const float mean = wave_sum(s) / (float)H;
+            float q2 = 0.f;
+#pragma unroll
+            for (int i = 0; i < LNB_MAXV; ++i)
+                if (i < nv && (lane + 64 * i) * 4 < H) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { const float d = xv[i][j] - mean; q2 += d * d; }
+                }
+            const float rstd = 1.0f / sqrtf(wave_sum(q2) / (float)H + eps);
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int i = 0; i < LNB_MAXV; ++i)
+                if (i < nv && (lane + 64 * i) * 4 < H) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float gy = dv[i][j] * gg[i][j];
+                        s1 += gy;
+                        s2 += gy * ((xv[i][j] - mean) * rstd);
+                    }
+                }
+            s1 = wave_sum(s1) / (float)H;
+            s2 = wave_sum(s2) / (float)H;
+#pragma unroll
+            for (int i = 0; i < LNB_MAXV; ++i)
+                if (i < nv && (lane + 64 * i) * 4 < H) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float xh = (xv[i][j] - mean) * rstd;
+                        acc[i][j] += rstd * (dv[i][j] * gg[i][j] - s1 - xh * s2);
+                    }
+                }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < LNB_MAXV; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) red[wave][(lane + 64 * i) * 4 + j] = acc[i][j];
+    __syncthreads();
+    for (int c = threadIdx.x; c < H; c += 256) dtmpl[(size_t)slot * H + c] = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+}
+
+int soft_template_bwd(const float* dy, const int64_t* ids, const int64_t* tt, const int64_t* pos, const float* tmpl, int n_slots, const float* posw,
+                      const float* typew, const float* g, float eps, float* dtmpl, int B, int Lt, int L, int H, int max_pos, int type_vocab,
+                      hipStream_t s, const DropSpec* in_drop) {
+    if (B <= 0 || Lt <= 0 || L < Lt || H % 4 || H > 256 * LNB_MAXV || n_slots < 1 || max_pos <= 0 || type_vocab <= 0) return CPT_ERR_SHAPE;
+    if (!dy || !ids || !tmpl || !posw || !typew || !g || !dtmpl) return CPT_ERR_NULL;
+    if (!pos && Lt > max_pos) return CPT_ERR_SHAPE;
+    soft_template_bwd_kernel<<<dim3(n_slots), dim3(256), 0, s>>>(dy, ids, tt, pos, tmpl, posw, typew, g, eps, dtmpl, B, Lt, L, H, max_pos, type_vocab,
+                                                                 in_drop ? *in_drop : DropSpec{});
     return CPT_OK;
 }
 

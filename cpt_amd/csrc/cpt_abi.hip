@@ -535,6 +535,7 @@ struct Fwd {
     int B, Lt, Li, L, M, H, I;  // M = B * L, the rows that exist (the folded encoder is launched for p.Me)
     int dt; bool lp;            // = p.dt, p.lp
     float* x_f32; void* x_lp; void* qkv; void* ctx; float* pre; float* a_f32; void* a_lp; void* ffn;
+    const float* tmpl; int n_slots;      // soft template (cpt_model_fwd_soft): text ids in (0, n_slots) read their word row from it; NULL: none
     // Folded bf16 encoder, 3-byte residual stream (common.h r3_encode): the pre-LayerNorm sums live as bf16 hi (x_lp / a_lp, the GEMM operands) +
     // int8 lo (the head of the x_f32 / a_f32 regions, which hold no fp32 tensor in this mode); the producers read and write
     // 3 + 3 bytes per element instead of 4 + 6, and the embedding kernels write their rows in that form directly.
@@ -563,13 +564,13 @@ struct Fwd {
         if (embed_pad) {
             Scope sc(CPT_K_EMBED, s);
             TRY(cpt::embed_ln_pad_cast(b->input_ids, b->token_type, b->position_ids, m->word_emb, m->pos_emb, m->type_emb, m->emb_ln_g, m->emb_ln_b, d.ln_eps,
-                                       x_lp, x_lo(), B, Lt, L, H, d.vocab, d.max_pos, d.type_vocab, b->img_feats, ws + w.imgp, B * Li, d.img_dim, d.img_dim_pad, s, p.rpanel),
-                "embed_ln + pad_cast(img_feats)");
+                                       x_lp, x_lo(), B, Lt, L, H, d.vocab, d.max_pos, d.type_vocab, b->img_feats, ws + w.imgp, B * Li, d.img_dim, d.img_dim_pad, s, p.rpanel,
+                                       nullptr, nullptr, nullptr, nullptr, tmpl, n_slots), "embed_ln + pad_cast(img_feats)");
         } else {
             Scope sc(CPT_K_EMBED, s);
             TRY(cpt::embed_ln(b->input_ids, b->token_type, b->position_ids, m->word_emb, m->pos_emb, m->type_emb,
                               m->emb_ln_g, m->emb_ln_b, d.ln_eps, fold ? nullptr : x_f32, lp ? x_lp : nullptr, dt, B, Lt, L, H,
-                              d.vocab, d.max_pos, d.type_vocab, s, fold ? x_lo() : nullptr, p.rpanel), "embed_ln");
+                              d.vocab, d.max_pos, d.type_vocab, s, fold ? x_lo() : nullptr, p.rpanel, nullptr, nullptr, nullptr, tmpl, n_slots), "embed_ln");
         }
         if (Li > 0) {
             Scope sc(CPT_K_IMG, s);
@@ -839,8 +840,12 @@ struct Fwd {
 
 // seq_in_ws (cpt_model_fwd_rows): with CPT_OUT_SEQ the encoder output stays in the workspace (x_f32 / x_lp of fwd_layout), o->seq is not used
 static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* o, int flags,
-                     void* workspace, size_t workspace_bytes, void* stream, bool seq_in_ws) {
+                     void* workspace, size_t workspace_bytes, void* stream, bool seq_in_ws, const cpt_soft_template* soft = nullptr) {
     if (!m || !b || !o || !workspace) return abi_fail(CPT_ERR_NULL, "cpt_model_fwd: null argument");
+    if (soft && soft->tmpl) {
+        if (soft->n_slots < 2 || soft->n_slots > m->dims.vocab) return abi_fail(CPT_ERR_SHAPE, "cpt_model_fwd_soft: n_slots %d outside [2, vocabulary %d]", soft->n_slots, m->dims.vocab);
+        if ((uintptr_t)soft->tmpl & 15) return abi_fail(CPT_ERR_ALIGN, "cpt_model_fwd_soft: tmpl must be 16-byte aligned");
+    }
     const cpt_dims& d = m->dims;
     hipStream_t s = (hipStream_t)stream;
     const int B = b->B, Lt = b->Lt, Li = b->Li, L = Lt + Li, H = d.hidden;
@@ -870,7 +875,8 @@ static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
 
     unsigned char* ws = (unsigned char*)workspace;
     const Fwd c = {p, d, m, b, o, flags, cols, ws, w, s, ModeGemm{p.x3, p.dt, ws + w.split, s}, B, Lt, Li, L, p.M, H, d.inter, p.dt, p.lp,
-                   (float*)(ws + w.x_f32), ws + w.x_lp, ws + w.qkv, ws + w.ctx, (float*)(ws + w.pre), (float*)(ws + w.a_f32), ws + w.a_lp, ws + w.ffn};
+                   (float*)(ws + w.x_f32), ws + w.x_lp, ws + w.qkv, ws + w.ctx, (float*)(ws + w.pre), (float*)(ws + w.a_f32), ws + w.a_lp, ws + w.ffn,
+                   soft ? soft->tmpl : nullptr, (soft && soft->tmpl) ? soft->n_slots : 0};
     int rc = c.embed();
     if (rc == CPT_OK) rc = p.fold ? c.encoder_folded() : c.encoder_plain();
     if (rc == CPT_OK && (flags & CPT_OUT_SEQ) && !seq_in_ws) rc = c.seq_out();
@@ -882,6 +888,11 @@ static int model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* 
 int cpt_model_fwd(const cpt_model* m, const cpt_batch* b, const cpt_outputs* o, int flags,
                   void* workspace, size_t workspace_bytes, void* stream) {
     return model_fwd(m, b, o, flags, workspace, workspace_bytes, stream, false);
+}
+
+int cpt_model_fwd_soft(const cpt_model* m, const cpt_soft_template* st, const cpt_batch* b, const cpt_outputs* o, int flags,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    return model_fwd(m, b, o, flags, workspace, workspace_bytes, stream, false, st);
 }
 
 // ---- MLM head on a list of rows + full-vocabulary log-sum-exp (VG-CPT predicate scoring) -----------------------------------------
@@ -916,8 +927,8 @@ size_t cpt_fwd_rows_workspace_bytes(const cpt_dims* d, int B, int Lt, int Li, in
                     rows_layout(*d, make_plan(*d, B, Lt, Li, f3, true), n_rows, n_cols, f3).total);
 }
 
-int cpt_model_fwd_rows(const cpt_model* m, const cpt_batch* b, const int64_t* cols, int n_cols, float* logits, float* row_lse,
-                       void* workspace, size_t workspace_bytes, void* stream) {
+static int model_fwd_rows(const cpt_model* m, const cpt_soft_template* soft, const cpt_batch* b, const int64_t* cols, int n_cols, float* logits, float* row_lse,
+                          void* workspace, size_t workspace_bytes, void* stream) {
     if (!m || !b) return abi_fail(CPT_ERR_NULL, "cpt_model_fwd_rows: null argument");
     const cpt_dims& d = m->dims;
     hipStream_t s = (hipStream_t)stream;
@@ -957,7 +968,7 @@ int cpt_model_fwd_rows(const cpt_model* m, const cpt_batch* b, const int64_t* co
     unsigned char* ws = (unsigned char*)workspace;
     cpt_outputs o;
     memset(&o, 0, sizeof(o));
-    int rc = model_fwd(m, b, &o, eflags, workspace, workspace_bytes, stream, true);
+    int rc = model_fwd(m, b, &o, eflags, workspace, workspace_bytes, stream, true, soft);
     if (rc != CPT_OK) return rc;
 
     Scope sc(CPT_K_HEAD, s);
@@ -980,6 +991,16 @@ int cpt_model_fwd_rows(const cpt_model* m, const cpt_batch* b, const int64_t* co
         TRY(cpt::gather_cols(full, cols, logits, R, n_cols, V, s), "gather(column list)");
     }
     return CPT_OK;
+}
+
+int cpt_model_fwd_rows(const cpt_model* m, const cpt_batch* b, const int64_t* cols, int n_cols, float* logits, float* row_lse,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    return model_fwd_rows(m, nullptr, b, cols, n_cols, logits, row_lse, workspace, workspace_bytes, stream);
+}
+
+int cpt_model_fwd_rows_soft(const cpt_model* m, const cpt_soft_template* st, const cpt_batch* b, const int64_t* cols, int n_cols, float* logits,
+                            float* row_lse, void* workspace, size_t workspace_bytes, void* stream) {
+    return model_fwd_rows(m, st, b, cols, n_cols, logits, row_lse, workspace, workspace_bytes, stream);
 }
 
 int cpt_mean_logprob_scores(const float* logits, int n_cols, int n_rows, const float* row_lse, const int32_t* slot_row, int G, int K,

@@ -19,13 +19,17 @@ int gemm(int dtype, int epi, const void* A, int lda, const void* W, int ldw, con
 int embed_ln(const int64_t* ids, const int64_t* tt, const int64_t* pos, const float* word,
              const float* posw, const float* typew, const float* g, const float* bta, float eps,
              float* out_f32, void* out_lp, int lp_dtype, int B, int Lt, int L, int H, int vocab,
-             int max_pos, int type_vocab, hipStream_t s, void* out_lo = nullptr, int out_panel = 0, float* zero_f2 = nullptr, unsigned* zero_u1 = nullptr, const struct DropSpec* out_drop = nullptr);   // out_drop (round 6): hidden dropout on the output rows (site mask at element index row * H + col, as dropout_rows)   // zero_f2 / zero_u1 (round 6, training forward): two floats and one word cleared by the launch's first workgroup -- the loss accumulator and the finish ticket of the cross-entropy launch at the END of the same forward (no memset launch);   out_lo: rows leave in the 3-byte residual form (hi -> out_lp); out_panel: at their panel positions
+             int max_pos, int type_vocab, hipStream_t s, void* out_lo = nullptr, int out_panel = 0, float* zero_f2 = nullptr, unsigned* zero_u1 = nullptr, const struct DropSpec* out_drop = nullptr,
+             const float* tmpl = nullptr, int n_slots = 0);      // tmpl [n_slots][H] (soft template, cpt_hip.h): ids in (0, n_slots) read their word row from it
+     // out_drop (round 6): hidden dropout on the output rows (site mask at element index row * H + col, as dropout_rows)   // zero_f2 / zero_u1 (round 6, training forward): two floats and one word cleared by the launch's first workgroup -- the loss accumulator and the finish ticket of the cross-entropy launch at the END of the same forward (no memset launch);   out_lo: rows leave in the 3-byte residual form (hi -> out_lp); out_panel: at their panel positions
 
 // bf16 inference: embed_ln (3-byte or bf16 output rows) and pad_cast(bf16) of the region features in ONE launch (they touch disjoint data)
 int embed_ln_pad_cast(const int64_t* ids, const int64_t* tt, const int64_t* pos, const float* word, const float* posw, const float* typew,
                       const float* g, const float* bta, float eps, void* out_lp, void* out_lo, int B, int Lt, int L, int H, int vocab,
                       int max_pos, int type_vocab, const float* x, void* xo, int R, int K, int Kp, hipStream_t s, int out_panel = 0,
-                      float* out_f32 = nullptr, float* zero_f2 = nullptr, unsigned* zero_u1 = nullptr, const struct DropSpec* out_drop = nullptr);     // out_f32 / zero_*: the training forward's fp32 residual rows and cleared words (embed_ln above);   out_panel (round 5): out_lp / out_lo = the panel-layout residual stream
+                      float* out_f32 = nullptr, float* zero_f2 = nullptr, unsigned* zero_u1 = nullptr, const struct DropSpec* out_drop = nullptr,
+                      const float* tmpl = nullptr, int n_slots = 0);      // tmpl / n_slots: as embed_ln
+       // out_f32 / zero_*: the training forward's fp32 residual rows and cleared words (embed_ln above);   out_panel (round 5): out_lp / out_lo = the panel-layout residual stream
 
 int layernorm_rows(const float* x, const float* g, const float* bta, float eps, float* out_f32,
                    void* out_lp, int lp_dtype, int R, int H, int grp, int grp_stride, int grp_off,
@@ -92,6 +96,7 @@ struct LnBwdExtra {
                               // the embedding dropout's backward on the region rows, instead of a dropout pass over all rows in front); thresh 0: none
     const unsigned short* keep_bits;   // [R][64] the forward pass's keep bits (layernorm_rows_ex keep_out): bit 4 i + j of word [row][lane] = element (lane + 64 i) * 4 + j;
                               // the mask is then read, not regenerated (the Philox rounds were ~1/3 of the launch's VALU time); H <= 1024
+    int no_sums;              // frozen model (cpt_train_bwd_soft): the launch forms no column sums at all -- dg, db, dbias and part are not used (NULL)
 };
 int ln_bwd_part_rows(int R);
 int ln_bwd(const float* dy, const float* x, const float* g, float eps, float* dx, void* dx_lp, int lp_dtype,
@@ -103,6 +108,11 @@ int embed_bwd(const float* dy, const int64_t* ids, const int64_t* tt, const int6
               const float* posw, const float* typew, const float* g, float eps, float* dword, float* dposw,
               float* dtypew, float* dg, float* db, int B, int Lt, int L, int H, int vocab, int max_pos,
               int type_vocab, hipStream_t s, const DropSpec* in_drop = nullptr);     // in_drop (round 6): BertEmbeddings' dropout applied to dy as it is read (element index (b L + t) H + col)
+// Soft template (cpt_hip.h cpt_soft_template): the embedding LayerNorm's backward (with the embedding dropout's backward, as embed_bwd) on the text rows whose
+// id lies in (0, n_slots), their word-row gradients summed per slot into dtmpl [n_slots][H] -- written whole, in row order, no atomics; no table is touched
+int soft_template_bwd(const float* dy, const int64_t* ids, const int64_t* tt, const int64_t* pos, const float* tmpl, int n_slots, const float* posw,
+                      const float* typew, const float* g, float eps, float* dtmpl, int B, int Lt, int L, int H, int max_pos, int type_vocab,
+                      hipStream_t s, const DropSpec* in_drop = nullptr);
 // pruned last layer (round 6): out_a[b] = a[b][pos[b]] (bf16 rows), out_b[b] = bb[b][pos[b]] (fp32 rows) in one launch; and its inverse for the
 // backward: za [B][L][H] bf16 and zb [B][L][H] fp32 zero except row (b, pos[b]) = a_r[b] / b_r[b] (one launch: fill + rows)
 int tail_gather2(const void* a, const float* bb, const int64_t* pos, void* out_a, float* out_b, int B, int L, int H, hipStream_t s);

@@ -285,6 +285,7 @@ struct EmbedArgs {
     int out_panel;      // round 5: out_lp / out_lo are the panel-layout residual stream (3-byte form)
     float* zero_f2; unsigned* zero_u1;      // round 6 (training forward): cleared by the first workgroup (kernels.h)
     DropSpec odrop;                         // round 6 (training forward): BertEmbeddings' dropout on the output rows (thresh 0: none)
+    const float* tmpl; int n_slots;         // soft template (cpt_hip.h cpt_soft_template): ids in (0, n_slots) read their word row from tmpl [n_slots][H]; NULL: none
 };
 // ERW rows per wave (round 6: 2 -- every gather of both rows in flight before the first row is reduced; with one row per wave the launch ran at the
 // latency of its ids -> table rows -> reduce -> store chain, 0.47 of 8 TB/s on the unique-bytes model at 4480 rows).  Per-row arithmetic unchanged: same bits.
@@ -317,17 +318,19 @@ __device__ __forceinline__ void embed_ln_block(const EmbedArgs& a, int block) {
         tid[u] = tt ? tt[r] : 0;
     }
     f32x4 v[ERW][MAXV];
+    const float* wrow[ERW];
 #pragma unroll
     for (int u = 0; u < ERW; ++u) {
         // out-of-range ids would be a host bug; clamp so the kernel never faults
         wid[u] = wid[u] < 0 ? 0 : (wid[u] >= vocab ? vocab - 1 : wid[u]);
         pid[u] = pid[u] < 0 ? 0 : (pid[u] >= max_pos ? max_pos - 1 : pid[u]);
         tid[u] = tid[u] < 0 ? 0 : (tid[u] >= type_vocab ? type_vocab - 1 : tid[u]);
+        wrow[u] = (a.tmpl && wid[u] > 0 && wid[u] < a.n_slots) ? a.tmpl + (size_t)wid[u] * H : word + (size_t)wid[u] * H;      // (one row per wave: a uniform choice)
 #pragma unroll
         for (int i = 0; i < MAXV; ++i) {
             const int c = (lane + 64 * i) * 4;
             if (i < nv && c < H) {
-                const f32x4 aw = *reinterpret_cast<const f32x4*>(word + (size_t)wid[u] * H + c);
+                const f32x4 aw = *reinterpret_cast<const f32x4*>(wrow[u] + c);
                 const f32x4 p = *reinterpret_cast<const f32x4*>(posw + (size_t)pid[u] * H + c);
                 const f32x4 q = *reinterpret_cast<const f32x4*>(typew + (size_t)tid[u] * H + c);
 #pragma unroll
@@ -355,7 +358,8 @@ __global__ __launch_bounds__(ROW_THREADS) void embed_ln_kernel(EmbedArgs a) { em
 int embed_ln(const int64_t* ids, const int64_t* tt, const int64_t* pos, const float* word,
              const float* posw, const float* typew, const float* g, const float* bta, float eps,
              float* out_f32, void* out_lp, int lp_dtype, int B, int Lt, int L, int H, int vocab,
-             int max_pos, int type_vocab, hipStream_t s, void* out_lo, int out_panel, float* zero_f2, unsigned* zero_u1, const DropSpec* out_drop) {
+             int max_pos, int type_vocab, hipStream_t s, void* out_lo, int out_panel, float* zero_f2, unsigned* zero_u1, const DropSpec* out_drop,
+             const float* tmpl, int n_slots) {
     if (B <= 0 || Lt <= 0 || L < Lt || H % 4 || H > 256 * MAXV) return CPT_ERR_SHAPE;
     if (out_panel && (!out_lo || out_f32 || H % 16)) return CPT_ERR_SHAPE;
     if (out_lo && !(out_lp && lp_dtype == CPT_BF16)) return CPT_ERR_DTYPE;
@@ -363,7 +367,7 @@ int embed_ln(const int64_t* ids, const int64_t* tt, const int64_t* pos, const fl
     if (!pos && Lt > max_pos) return CPT_ERR_SHAPE;
     const int erw = (B * Lt >= EMB_RPW2_ROWS && H == 768) ? 2 : 1;
     dim3 grid((B * Lt + 4 * erw - 1) / (4 * erw)), block(ROW_THREADS);
-    EmbedArgs a{ids, tt, pos, word, posw, typew, g, bta, eps, out_f32, out_lp, (signed char*)out_lo, B, Lt, L, H, vocab, max_pos, type_vocab, out_panel ? 1 : 0, zero_f2, zero_u1, (out_drop && !out_panel) ? *out_drop : DropSpec{}};
+    EmbedArgs a{ids, tt, pos, word, posw, typew, g, bta, eps, out_f32, out_lp, (signed char*)out_lo, B, Lt, L, H, vocab, max_pos, type_vocab, out_panel ? 1 : 0, zero_f2, zero_u1, (out_drop && !out_panel) ? *out_drop : DropSpec{}, n_slots > 1 ? tmpl : nullptr, n_slots};
     if (out_lp && lp_dtype == CPT_BF16) { if (H == 768 && erw == 2) embed_ln_kernel<bf16, 3, 2><<<grid, block, 0, s>>>(a); else if (H == 768) embed_ln_kernel<bf16, 3><<<grid, block, 0, s>>>(a); else embed_ln_kernel<bf16><<<grid, block, 0, s>>>(a); }
     else { a.out_lo = nullptr; if (H == 768) embed_ln_kernel<float, 3><<<grid, block, 0, s>>>(a); else embed_ln_kernel<float><<<grid, block, 0, s>>>(a); }
     return CPT_OK;
@@ -435,7 +439,7 @@ __global__ __launch_bounds__(256) void embed_pad_kernel(EmbedArgs a, const float
 int embed_ln_pad_cast(const int64_t* ids, const int64_t* tt, const int64_t* pos, const float* word, const float* posw, const float* typew,
                       const float* g, const float* bta, float eps, void* out_lp, void* out_lo, int B, int Lt, int L, int H, int vocab,
                       int max_pos, int type_vocab, const float* x, void* xo, int R, int K, int Kp, hipStream_t s, int out_panel,
-                      float* out_f32, float* zero_f2, unsigned* zero_u1, const DropSpec* out_drop) {
+                      float* out_f32, float* zero_f2, unsigned* zero_u1, const DropSpec* out_drop, const float* tmpl, int n_slots) {
     if (out_panel && (!out_lo || H % 16 || out_f32)) return CPT_ERR_SHAPE;
     if (B <= 0 || Lt <= 0 || L < Lt || H % 4 || H > 256 * MAXV || R <= 0 || K <= 0 || Kp < K || Kp % 8) return CPT_ERR_SHAPE;
     if (!ids || !word || !posw || !typew || !g || !bta || !out_lp || !x || !xo) return CPT_ERR_NULL;
@@ -443,7 +447,7 @@ int embed_ln_pad_cast(const int64_t* ids, const int64_t* tt, const int64_t* pos,
     if (((uintptr_t)xo % 16) || ((uintptr_t)x % 8)) return CPT_ERR_ALIGN;
     const size_t n = (size_t)R * (Kp / 8);
     const int npad = (int)((n + 256 * PC_UNR - 1) / (256 * PC_UNR));
-    EmbedArgs a{ids, tt, pos, word, posw, typew, g, bta, eps, out_f32, out_lp, (signed char*)out_lo, B, Lt, L, H, vocab, max_pos, type_vocab, out_panel ? 1 : 0, zero_f2, zero_u1, (out_drop && !out_panel) ? *out_drop : DropSpec{}};
+    EmbedArgs a{ids, tt, pos, word, posw, typew, g, bta, eps, out_f32, out_lp, (signed char*)out_lo, B, Lt, L, H, vocab, max_pos, type_vocab, out_panel ? 1 : 0, zero_f2, zero_u1, (out_drop && !out_panel) ? *out_drop : DropSpec{}, n_slots > 1 ? tmpl : nullptr, n_slots};
     if (H == 768) embed_pad_kernel<3><<<dim3(npad + (B * Lt + 3) / 4), dim3(256), 0, s>>>(a, x, (bf16*)xo, R, K, Kp, npad);
     else embed_pad_kernel<MAXV><<<dim3(npad + (B * Lt + 3) / 4), dim3(256), 0, s>>>(a, x, (bf16*)xo, R, K, Kp, npad);
     return CPT_OK;

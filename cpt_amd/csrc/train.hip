@@ -378,6 +378,7 @@ const DenseLnNames WHAT_FD = {"gemm(ffn down, K split)", "partials+dropout(ffn d
 struct TrainFwd : TrainCtx {
     const cpt_rel2* x;      // the second relation head of VCR Q->AR (cpt_train_fwd_rel2), NULL for every other model
     const cpt_outputs* o;
+    const float* tmpl; int n_slots;      // soft template (cpt_train_fwd_soft): text ids in (0, n_slots) read their word row from it; NULL for every other call
     unsigned* ce_ticket() const { return (unsigned*)at(w.loss + 16); }      // finish ticket of the cross-entropy launch at the end of the forward
 
     int embed() const {
@@ -390,10 +391,10 @@ struct TrainFwd : TrainCtx {
         if (emb_pad)
             TRY(cpt::embed_ln_pad_cast(b->input_ids, b->token_type, b->position_ids, m->word_emb, m->pos_emb, m->type_emb, m->emb_ln_g, m->emb_ln_b, d.ln_eps,
                                        LB(0, w.o_xin), nullptr, B, Lt, L, H, d.vocab, d.max_pos, d.type_vocab, b->img_feats, at(w.imgp), B * Li, d.img_dim, d.img_dim_pad, s, 0,
-                                       x_f32, o->loss, ce_ticket(), ph ? &edrop : nullptr), "embed_ln + dropout + pad_cast(img_feats)");
+                                       x_f32, o->loss, ce_ticket(), ph ? &edrop : nullptr, tmpl, n_slots), "embed_ln + dropout + pad_cast(img_feats)");
         else
             TRY(cpt::embed_ln(b->input_ids, b->token_type, b->position_ids, m->word_emb, m->pos_emb, m->type_emb, m->emb_ln_g, m->emb_ln_b, d.ln_eps, x_f32,
-                              LB(0, w.o_xin), dt, B, Lt, L, H, d.vocab, d.max_pos, d.type_vocab, s, nullptr, 0, o->loss, ce_ticket(), ph ? &edrop : nullptr), "embed_ln + dropout");
+                              LB(0, w.o_xin), dt, B, Lt, L, H, d.vocab, d.max_pos, d.type_vocab, s, nullptr, 0, o->loss, ce_ticket(), ph ? &edrop : nullptr, tmpl, n_slots), "embed_ln + dropout");
         if (Li <= 0) return CPT_OK;
         if (!emb_pad) TRY(cpt::pad_cast(b->img_feats, at(w.imgp), dt, B * Li, d.img_dim, d.img_dim_pad, s), "pad_cast(img_feats)");
         TRY(gm(CPT_EPI_NONE, at(w.imgp), d.img_dim_pad, m->w_img, d.img_dim_pad, m->b_img, nullptr, 0, f32(w.imgpre), CPT_F32, H, B * Li, H, d.img_dim_pad), "gemm(img_embedding)");
@@ -542,8 +543,18 @@ struct TrainFwd : TrainCtx {
     }
 };
 
+int check_soft(const cpt_model* m, const cpt_soft_template* st, bool need_grad, const char* who) {
+    if (!st || !st->tmpl) return abi_fail(CPT_ERR_NULL, "%s: the soft template (tmpl) is NULL", who);
+    if (need_grad && !st->g_tmpl) return abi_fail(CPT_ERR_NULL, "%s: g_tmpl is NULL", who);
+    if (st->n_slots < 2 || st->n_slots > m->dims.vocab) return abi_fail(CPT_ERR_SHAPE, "%s: n_slots %d outside [2, vocabulary %d]", who, st->n_slots, m->dims.vocab);
+    if (((uintptr_t)st->tmpl & 15) || (need_grad && ((uintptr_t)st->g_tmpl & 15))) return abi_fail(CPT_ERR_ALIGN, "%s: the template tensors must be 16-byte aligned", who);
+    if (!m->w_tr || !m->w_dec)
+        return abi_fail(CPT_ERR_SHAPE, "%s: soft-template tuning runs on the MLM head; the NSP-CPT heads (pooler + relation heads) are not supported", who);
+    return CPT_OK;
+}
+
 int train_fwd_impl(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, const cpt_outputs* o, void* workspace, size_t workspace_bytes, void* stream,
-                   cpt_bucket_fn before_bucket, void* user, const cpt_dropout* drop) {
+                   cpt_bucket_fn before_bucket, void* user, const cpt_dropout* drop, const cpt_soft_template* soft = nullptr) {
     if (!m || !b || !o || !workspace) return abi_fail(CPT_ERR_NULL, "cpt_train_fwd: null argument");
     PASS(check_drop(drop, "cpt_train_fwd"));
     const TrainPlan p = make_train_plan(m, x, b, drop);
@@ -564,6 +575,7 @@ int train_fwd_impl(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, co
     TrainFwd f = {};
     set_ctx(f, p, m, b, workspace, stream, drop, before_bucket, user);
     f.x = x; f.o = o;
+    if (soft) { f.tmpl = soft->tmpl; f.n_slots = soft->n_slots; }
     PASS(f.embed());
     for (int l = 0; l < m->dims.layers; ++l) PASS(p.tail && l == m->dims.layers - 1 ? f.layer_tail(l) : f.layer(l));
     return p.nsp ? f.head_nsp() : f.head_mlm();
@@ -831,6 +843,147 @@ int train_bwd_impl(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, co
     return t.embeddings(st);
 }
 
+// ---- backward of a frozen model (cpt_train_bwd_soft) ----------------------------------------------------------------------------------------
+// The walk of TrainBwd with everything that only a parameter gradient needs taken out: the same head, LayerNorm backwards (LnBwdExtra::no_sums:
+// no gain / shift / bias sums, no partial tables, no carried jobs), data-gradient GEMMs with the GELU gradient, attention backward, dropout and
+// residual handling under the same plan -- the pruned last layer, the K-split partial matrices the next LayerNorm backward adds, the bf16
+// partial pair, the unfused fp32 / bf16x3 branch -- and no weight-gradient GEMM, column sum, zero launch or region-side launch.  It ends in
+// the template's gradient (bwd.hip soft_template_bwd), the only tensor outside the workspace it writes.
+struct FrozenBwd : TrainCtx {
+    const cpt_soft_template* soft; float loss_scale; const float* loss_scale_dev;
+    const float* dpre_f() const { return f32(ph ? w.dmask : w.dpre); }
+    const void* dpre_in() const { return dt == CPT_BF16 ? at(ph ? w.dmask_lp : w.dpre_lp) : (const void*)dpre_f(); }
+
+    int head_mlm() const {
+        float* dt2 = f32(w.dt2); float* duh = f32(w.duh);
+        TRY(cpt::scale_cast(f32(w.dlogits), f32(w.loss), loss_scale, loss_scale_dev, at(w.dl_lp), dt, Rh, V, Vp, s), "scale(dlogits)");
+        PASS(dgrad(at(w.dl_lp), Vp, Vp, m->w_dec, H, V, H, Rh, nullptr, dt2, CPT_F32, "dgrad(decoder)"));
+        cpt::LnBwdExtra e = {};
+        e.no_sums = 1;
+        TRY(cpt::ln_bwd(dt2, f32(w.uh), m->tr_ln_g, d.ln_eps, duh, dt == CPT_BF16 ? at(w.duh_lp) : nullptr, dt, nullptr, nullptr, Rh, H, Rh, 0, 0, 1, s,
+                        nullptr, 0, nullptr, nullptr, &e), "ln_bwd(head)");
+        const void* duh_in = dt == CPT_BF16 ? at(w.duh_lp) : (const void*)duh;
+        return dgrad(duh_in, H, H, m->w_tr, H, H, H, Rh, nullptr, f32(w.drows), CPT_F32, "dgrad(head transform)");
+    }
+
+    // one LayerNorm backward with the dropout mask of the dense output in front of it (TrainBwd::ln_bwd_side without its sums)
+    int ln_bwd_side(int l, const LnBwdSide& q) const {
+        float* dpre = f32(w.dpre);
+        cpt::LnBwdExtra e = {};
+        e.no_sums = 1;
+        if (!fuse_db) {
+            TRY(cpt::ln_bwd(q.dy, LBf(l, q.pre), q.g, d.ln_eps, dpre, nullptr, dt, nullptr, nullptr, M, H, M, 0, 0, 0, s, nullptr, 0, nullptr, nullptr, &e), q.what->ln_bwd);
+            if (ph) TRY(cpt::dropout_rows(dpre, nullptr, f32(w.dmask), nullptr, dt, M, H, site(q.site), s), q.what->dropout);
+            return CPT_OK;
+        }
+        const cpt::DropSpec sp = site(q.site);
+        e.stats = LBf(l, q.st); e.keep_bits = (const unsigned short*)LB(l, q.kb);
+        if (q.S > 1) { e.dy_parts = q.S; e.dy_stride = (size_t)M * H; e.dy_resid = dpre; e.dy_parts_bf16 = q.Sbf16; }
+        TRY(cpt::ln_bwd(q.S > 1 ? f32(w.tA) : q.dy, LBf(l, q.pre), q.g, d.ln_eps, dpre, q.out_lp, dt, nullptr, nullptr, M, H, M, 0, 0, 0, s, nullptr, 0,
+                        ph ? &sp : nullptr, nullptr, &e), q.what->fused);
+        return CPT_OK;
+    }
+
+    // attention backward of layer l and the data gradient into dx
+    int attention(int l, BwdState& st) const {
+        const cpt_layer& y = m->layers[l];
+        void* dbig = at(w.dbig);
+        const cpt::DropSpec da_spec = site(1 + 3 * l, true);
+        if (x3_attn)
+            TRY(cpt::attention_bwd_x3(LBf(l, w.o_qkv), b->attn_mask, (const float*)at(w.dctx), (float*)dbig, B, L, d.heads, s, pa ? &da_spec : nullptr, nullptr),
+                "attention_bwd (split operands)");
+        else
+            TRY(cpt::attention_bwd(dt, LB(l, w.o_qkv), b->attn_mask, at(w.dctx), dbig, B, L, d.heads, s, pa ? &da_spec : nullptr, nullptr, m3d,
+                                   attn_stats ? LB(l, w.o_ctx) : nullptr, attn_stats ? LBf(l, w.o_ast) : nullptr), "attention_bwd");
+        // (layer 0's result feeds the template gradient: complete; above that a K-split launch leaves its partial matrices to the next LayerNorm backward)
+        st.dxS = 1;
+        const int rc = dgrad(dbig, 3 * H, 3 * H, y.w_qkv, H, 3 * H, H, M, f32(w.dpre), f32(w.dx), CPT_F32, "dgrad(qkv)+residual", nullptr, nullptr, 0, (fuse_db && l > 0) ? &st.dxS : nullptr, 1);
+        st.dxB = (st.dxS == 2 && M >= 2048) ? 1 : 0;
+        return rc;
+    }
+
+    // the pruned last layer on the B head rows (TrainBwd::layer_tail)
+    int layer_tail(int l, BwdState& st) const {
+        const cpt_layer& y = m->layers[l];
+        const cpt::RowMap rm = {b->mask_pos, L, 1};
+        const cpt::DropSpec sp2 = site(3 + 3 * l), sp1 = site(2 + 3 * l);
+        float* dpre_r = f32(w.t_dpre); float* da_r = f32(w.t_da);
+        void* dlpF = at(w.t_dlpF); void* dlpA = at(w.t_dlpA); void* dbig_r = at(w.t_dbig); void* dctx_r = at(w.t_dctx);
+        cpt::LnBwdExtra e2 = {};
+        e2.no_sums = 1; e2.stats = f32(w.t_st2); e2.drop_rows = rm; e2.keep_bits = (const unsigned short*)at(w.t_kb2);
+        TRY(cpt::ln_bwd(f32(w.drows), f32(w.t_pre2), y.ln2_g, d.ln_eps, dpre_r, dlpF, dt, nullptr, nullptr, B, H, B, 0, 0, 0, s, nullptr, 0,
+                        ph ? &sp2 : nullptr, nullptr, &e2), "ln_bwd(ffn, head rows)");
+        PASS(dgrad(dlpF, H, H, y.w_out, I, H, I, B, nullptr, dbig_r, dt, "dgrad(ffn down)+gelu_bwd (head rows)", at(w.t_u)));
+        int daS = 1;
+        PASS(dgrad(dbig_r, I, I, y.w_in, H, I, H, B, dpre_r, da_r, CPT_F32, "dgrad(ffn up)+residual (head rows)", nullptr, nullptr, 0, &daS));
+        cpt::LnBwdExtra e1 = {};
+        e1.no_sums = 1; e1.stats = f32(w.t_st1); e1.drop_rows = rm; e1.keep_bits = (const unsigned short*)at(w.t_kb1);
+        if (daS > 1) { e1.dy_parts = daS; e1.dy_stride = (size_t)B * H; e1.dy_resid = dpre_r; }
+        TRY(cpt::ln_bwd(daS > 1 ? f32(w.tA) : da_r, f32(w.t_pre1), y.ln1_g, d.ln_eps, dpre_r, dlpA, dt, nullptr, nullptr, B, H, B, 0, 0, 0, s,
+                        nullptr, 0, ph ? &sp1 : nullptr, nullptr, &e1), "ln_bwd(attn, head rows)");
+        PASS(dgrad(dlpA, H, H, y.w_ao, H, H, H, B, nullptr, dctx_r, dt, "dgrad(attn out, head rows)"));
+        TRY(cpt::tail_scatter2(dctx_r, dpre_r, rm.pos, at(w.dctx), f32(w.dpre), B, L, H, s), "scatter(head rows of dctx, dpre)");
+        return attention(l, st);
+    }
+
+    int layer(int l, BwdState& st) const {
+        const cpt_layer& y = m->layers[l];
+        float* dpre = f32(w.dpre); void* dbig = at(w.dbig);
+        void* lp_out = at(ph ? w.dmask_lp : w.dpre_lp);
+        // x_out = LN2(pre2); pre2 = h W_out^T + b_out + a
+        LnBwdSide f = {};
+        f.what = &WHAT_LN2; f.dy = f32(w.dx); f.S = st.dxS; f.Sbf16 = st.dxB; f.pre = w.o_pre2; f.st = w.o_st2; f.kb = w.o_kb2;
+        f.g = y.ln2_g; f.site = 3 + 3 * l; f.out_lp = lp_out;
+        PASS(ln_bwd_side(l, f));
+        // h = gelu(u); u = a W_in^T + b_in: bf16 runs the GELU backward in the epilogue of the data-gradient GEMM (no bias sums here)
+        int rc = dt == CPT_BF16 ? dgrad(dpre_in(), H, H, y.w_out, I, H, I, M, nullptr, dbig, dt, "dgrad(ffn down)+gelu_bwd", LB(l, w.o_u)) : NOT_FUSED;
+        if (rc == NOT_FUSED) {
+            PASS(dgrad(dpre_in(), H, H, y.w_out, I, H, I, M, nullptr, dbig, dt, "dgrad(ffn down)"));
+            TRY(cpt::gelu_bwd(dbig, LB(l, w.o_u), dbig, dt, (size_t)M * I, s), "gelu_bwd");
+        } else if (rc) return rc;
+        int daS = 1;
+        PASS(dgrad(dbig, I, I, y.w_in, H, I, H, M, dpre, f32(w.da), CPT_F32, "dgrad(ffn up)+residual", nullptr, nullptr, 0, fuse_db ? &daS : nullptr, 1));
+        // a = LN1(pre1); pre1 = ctx W_ao^T + b_ao + x_in
+        LnBwdSide a = {};
+        a.what = &WHAT_LN1; a.dy = f32(w.da); a.S = daS; a.pre = w.o_pre1; a.st = w.o_st1; a.kb = w.o_kb1;
+        a.Sbf16 = (daS == 2 && M >= 2048) ? 1 : 0;
+        a.g = y.ln1_g; a.site = 2 + 3 * l; a.out_lp = lp_out;      // (no weight gradient still reads the FFN side's low-precision rows: one buffer serves both sides)
+        PASS(ln_bwd_side(l, a));
+        PASS(dgrad(dpre_in(), H, H, y.w_ao, H, H, H, M, nullptr, at(w.dctx), dt, "dgrad(attn out)"));
+        return attention(l, st);
+    }
+
+    // the template's gradient: the embedding LayerNorm's backward on the slot rows; the region rows of dx and every table go unread and unwritten
+    int template_grad() const {
+        const cpt::DropSpec edrop = site(0);
+        TRY(cpt::soft_template_bwd(f32(w.dx), b->input_ids, b->token_type, b->position_ids, soft->tmpl, soft->n_slots, m->pos_emb, m->type_emb, m->emb_ln_g,
+                                   d.ln_eps, soft->g_tmpl, B, Lt, L, H, d.max_pos, d.type_vocab, s, ph ? &edrop : nullptr), "soft_template_bwd + dropout_bwd(embeddings)");
+        return CPT_OK;
+    }
+};
+
+int frozen_bwd_impl(const cpt_model* m, const cpt_soft_template* soft, const cpt_batch* b, float loss_scale, const float* loss_scale_dev,
+                    void* workspace, size_t workspace_bytes, void* stream, const cpt_dropout* drop) {
+    if (!m || !b || !workspace) return abi_fail(CPT_ERR_NULL, "cpt_train_bwd_soft: null argument");
+    PASS(check_soft(m, soft, true, "cpt_train_bwd_soft"));
+    PASS(check_drop(drop, "cpt_train_bwd_soft"));
+    const TrainPlan p = make_train_plan(m, nullptr, b, drop);
+    PASS(check_common(m, b, workspace, workspace_bytes, p, "cpt_train_bwd_soft"));
+    FrozenBwd t = {};
+    set_ctx(t, p, m, b, workspace, stream, drop, nullptr, nullptr);
+    t.soft = soft; t.loss_scale = loss_scale; t.loss_scale_dev = loss_scale_dev;
+    PASS(t.head_mlm());
+    if (!p.tail) {      // (pruned last layer: drows IS the gradient of that layer's compact output)
+        hipError_t e = hipMemsetAsync(t.f32(p.w.dx), 0, (size_t)p.M * p.H * 4, t.s);
+        if (e != hipSuccess) return abi_fail(CPT_ERR_HIP - (int)e, "zero dx: %s", hipGetErrorString(e));
+        TRY(cpt::scatter_rows_add(t.f32(p.w.drows), b->mask_pos, t.f32(p.w.dx), p.Rh, p.L, p.H, t.s, b->n_rows > 0 ? b->row_seq : nullptr, p.B), "scatter([MASK] rows)");
+    }
+    BwdState st = {};
+    st.ready_after_triple = -1; st.dxS = 1;
+    for (int l = m->dims.layers - 1; l >= 0; --l) PASS(p.tail && l == m->dims.layers - 1 ? t.layer_tail(l, st) : t.layer(l, st));
+    return t.template_grad();
+}
+
 }  // namespace
 
 extern "C" {
@@ -992,6 +1145,18 @@ int cpt_train_bwd_rel2(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b
 int cpt_train_zero_grads_rel2(const cpt_model* m, const cpt_rel2* x, const cpt_model_grads* g, int Li, void* stream) {
     if (!x) return abi_fail(CPT_ERR_NULL, "cpt_train_zero_grads_rel2: the second head (x) is NULL");
     return zero_grads_impl(m, x, g, Li, stream);
+}
+
+int cpt_train_fwd_soft(const cpt_model* m, const cpt_soft_template* st, const cpt_batch* b, const cpt_outputs* o, void* workspace,
+                       size_t workspace_bytes, void* stream, cpt_bucket_fn before_bucket, void* user, const cpt_dropout* drop) {
+    if (!m) return abi_fail(CPT_ERR_NULL, "cpt_train_fwd_soft: null argument");
+    PASS(check_soft(m, st, false, "cpt_train_fwd_soft"));
+    return train_fwd_impl(m, nullptr, b, o, workspace, workspace_bytes, stream, before_bucket, user, drop, st);
+}
+
+int cpt_train_bwd_soft(const cpt_model* m, const cpt_soft_template* st, const cpt_batch* b, float loss_scale, const float* loss_scale_dev,
+                       void* workspace, size_t workspace_bytes, void* stream, const cpt_dropout* drop) {
+    return frozen_bwd_impl(m, st, b, loss_scale, loss_scale_dev, workspace, workspace_bytes, stream, drop);
 }
 
 }  // extern "C"

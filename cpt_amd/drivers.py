@@ -193,6 +193,27 @@ def train_batch(model, optimizer, batches, opts, device, global_step=0):
     return _scheduled_pass(model, optimizer, batches, opts, device, global_step, _label_grid)
 
 
+def tune_soft_template(model, optimizer, batches, device):
+    """The template-tuning loop of explore/sgd_to_explore_template.py:396-412 on a model with a soft template attached
+    (cpt_amd/soft_prompt.py attach; ``optimizer`` is any torch optimizer over that one tensor -- the reference builds
+    ``AdamW([template], lr=0.02, eps=1e-8)``): per batch the label grid with the colour id at the [MASK] position, the loss divided
+    ADDITIONALLY by the batch size (:409), zero_grad / backward / step.  Returns the list of (divided) loss tensors.
+    The reference runs this loop on BertImgForPreTraining with next_sentence_label=0, so its loss also carries the contrastive term;
+    here it is REC_MLM_CPT's MLM loss alone."""
+    model.train()
+    losses = []
+    for host_batch in batches:
+        batch = {name: torch.as_tensor(t).to(device) for name, t in host_batch.items()}
+        optimizer.zero_grad()
+        loss = model(batch["input_ids"], batch["segment_ids"], batch["attention_mask"], img_feats=batch["img_feats"],
+                     masked_lm_labels=_label_grid(batch))[0]
+        loss = loss / batch["input_ids"].size(0)
+        loss.backward()
+        optimizer.step()
+        losses.append(loss.detach())
+    return losses
+
+
 # ---- VG-CPT (Oscar/oscar/fewshot/vg_cpt.py; launched by cmds/vg/_fsl.sh with 16 pairs per GPU) ------------------------------------
 def _vg_cat(chunk, device, per_pair, trim=False):
     """Concatenate pairs (dicts of prompts.assemble_vg_* arrays + img_feats) into one batch; mask_token_pos gets the pair's sequence

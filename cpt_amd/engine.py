@@ -481,6 +481,21 @@ class PackedModel(object):
             res["loss2"] = loss2[:2]
         return res
 
+    # ---- soft template (cpt_amd/soft_prompt.py) -------------------------------------------
+    def soft_template(self, grad=None):
+        """cpt_soft_template of the module's attached template (None without one): the tensor lives outside the flat buffer, so the
+        struct is made per call from the tensor itself.  grad: the (n_slots, H) tensor cpt_train_bwd_soft writes."""
+        from .soft_prompt import template_of
+        t = template_of(self.module)
+        if t is None:
+            return None
+        if t.device != self.flat.device or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("cpt_amd: the soft template must be a contiguous fp32 tensor on the model's device (%s), not %s on %s"
+                               % (self.flat.device, t.dtype, t.device))
+        if t.size(1) != self.cfg.hidden_size:
+            raise RuntimeError("cpt_amd: the soft template has %d columns, hidden size is %d" % (t.size(1), self.cfg.hidden_size))
+        return L.SoftTemplate(tmpl=t.data_ptr(), g_tmpl=L.ptr(grad), n_slots=int(t.size(0)))
+
     # ---- forward -------------------------------------------------------------------------
     def _buffer(self, key, need, zero=False, dtype=torch.uint8, device=None):
         """Grow-only cache of device buffers: the one kept under ``key`` while it is on the device (default: the parameters') and holds at
@@ -624,8 +639,13 @@ class PackedModel(object):
                      position_ids=L.ptr(position_ids), attn_mask=L.ptr(attention_mask), img_feats=L.ptr(img_feats),
                      mask_pos=L.ptr(mask_pos), labels=L.ptr(labels))
         ws = self.workspace(B, Lt, Li, flags)
-        L.check(L.lib().cpt_model_fwd(C.byref(m), C.byref(bt), C.byref(o), call_flags, ws.data_ptr(), ws.numel(),
-                                      L.stream_ptr()), "cpt_model_fwd")
+        soft = self.soft_template()
+        if soft is not None:
+            L.check(L.lib().cpt_model_fwd_soft(C.byref(m), C.byref(soft), C.byref(bt), C.byref(o), call_flags, ws.data_ptr(), ws.numel(),
+                                               L.stream_ptr()), "cpt_model_fwd_soft")
+        else:
+            L.check(L.lib().cpt_model_fwd(C.byref(m), C.byref(bt), C.byref(o), call_flags, ws.data_ptr(), ws.numel(),
+                                          L.stream_ptr()), "cpt_model_fwd")
         if flags & L.OUT_LOSS:
             acc = out["loss_acc"]
             out["loss"] = acc[0] / acc[1]       # mean over labelled rows (CrossEntropyLoss default)
@@ -663,8 +683,13 @@ class PackedModel(object):
                      mask_pos=mask_pos.data_ptr(), labels=None, n_rows=n, mask_3d=1 if mask3 else 0, row_seq=row_seq.data_ptr())
         need = L.lib().cpt_fwd_rows_workspace_bytes(C.byref(m.dims), B, Lt, Li, n, nc) if n > 0 else 0
         ws = self._buffer("rows", need) if need else self._ws.get("rows")
-        L.check(L.lib().cpt_model_fwd_rows(C.byref(m), C.byref(bt), L.ptr(cols), nc, out["logits"].data_ptr(), L.ptr(out["lse"]),
-                                           L.ptr(ws), ws.numel() if ws is not None else 0, L.stream_ptr()), "cpt_model_fwd_rows")
+        soft = self.soft_template()
+        if soft is not None:
+            L.check(L.lib().cpt_model_fwd_rows_soft(C.byref(m), C.byref(soft), C.byref(bt), L.ptr(cols), nc, out["logits"].data_ptr(), L.ptr(out["lse"]),
+                                                    L.ptr(ws), ws.numel() if ws is not None else 0, L.stream_ptr()), "cpt_model_fwd_rows_soft")
+        else:
+            L.check(L.lib().cpt_model_fwd_rows(C.byref(m), C.byref(bt), L.ptr(cols), nc, out["logits"].data_ptr(), L.ptr(out["lse"]),
+                                               L.ptr(ws), ws.numel() if ws is not None else 0, L.stream_ptr()), "cpt_model_fwd_rows")
         return out
 
 

@@ -22,6 +22,7 @@ from torch import nn
 from . import _lib as L
 from .modeling_bert import (BertImgModel, BertLMPredictionHead, _EngineMixin, _check_unsupported)
 from .modeling_utils import BertPreTrainedModel
+from .soft_prompt import frozen_step
 
 
 class REC_MLM_CPT(_EngineMixin, BertPreTrainedModel):
@@ -65,7 +66,9 @@ class REC_MLM_CPT(_EngineMixin, BertPreTrainedModel):
                 labels = labels[torch.arange(labels.size(0), device=labels.device), mask_token_pos]
         if vocab_columns is not None and (not rows or masked_lm_labels is not None):
             raise NotImplementedError("cpt_amd: vocab_columns goes with mask_token_pos and without masked_lm_labels")
-        if torch.is_grad_enabled() and masked_lm_labels is not None and self.bert.img_embedding.weight.requires_grad:
+        # a frozen model with a trainable soft template (cpt_amd/soft_prompt.py) trains too: the frozen step
+        soft = torch.is_grad_enabled() and masked_lm_labels is not None and frozen_step(self)
+        if torch.is_grad_enabled() and masked_lm_labels is not None and (soft or self.bert.img_embedding.weight.requires_grad):
             from .train import mlm_loss_with_grad
             if mask_token_pos is None:
                 # reference call form: a (B, L) grid with -1 everywhere except the [MASK] slot

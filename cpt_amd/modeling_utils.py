@@ -118,6 +118,8 @@ class PreTrainedModel(nn.Module):
         if state_dict is None:
             path = pretrained_model_name_or_path
             state_dict = torch.load(os.path.join(path, WEIGHTS_NAME) if os.path.isdir(path) else path, map_location="cpu")
+        from .soft_prompt import attach_from_state_dict
+        attach_from_state_dict(model, state_dict)      # a checkpoint of a prompt-tuned model carries its template (soft_prompt.KEY)
         info = model.adopt_state_dict(state_dict)
         who = model.__class__.__name__
         if info["missing_keys"]:

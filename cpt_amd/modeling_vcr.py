@@ -22,6 +22,8 @@ from .modeling_bert import BertImgModel, BertLMPredictionHead, _EngineMixin, _ch
 from .modeling_utils import BertPreTrainedModel
 
 
+from .soft_prompt import refuse_soft_training
+
 class NSPCPT(_EngineMixin, BertPreTrainedModel):
     _head = "nsp"
 
@@ -52,6 +54,8 @@ class NSPCPT(_EngineMixin, BertPreTrainedModel):
         if not isinstance(self.cls, nn.Linear):
             raise RuntimeError("cpt_amd: NSPCPT needs copy_from_pretraining_model() first (cls must be the "
                                "seq_relationship Linear, modeling_vcr.py:90-92)")
+        if torch.is_grad_enabled() and next_sentence_label is not None:
+            refuse_soft_training(self, "NSPCPT")
         if torch.is_grad_enabled() and next_sentence_label is not None and self.cls.weight.requires_grad:
             # few-shot fine-tuning (fewshot/vcr_nsp_cpt.py:425-470): loss with gradients through the HIP backward
             from .train import mlm_loss_with_grad
@@ -112,6 +116,8 @@ class VCRQAR_NSPCPT(_EngineMixin, BertPreTrainedModel):
                                "seq_relationship Linears, modeling_vcr.py:206-209)")
 
     def _training(self, labels):
+        if torch.is_grad_enabled() and labels is not None:
+            refuse_soft_training(self, "VCRQAR_NSPCPT")
         return torch.is_grad_enabled() and labels is not None and (self.cls_ans.weight.requires_grad or self.cls_rat.weight.requires_grad)
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, next_sentence_label=None,

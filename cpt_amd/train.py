@@ -280,6 +280,78 @@ class _MLMLoss(torch.autograd.Function):
         return None, None, None, None, None
 
 
+class _SoftTemplateLoss(torch.autograd.Function):
+    """The frozen step (cpt_amd/soft_prompt.py): cpt_train_fwd_soft / cpt_train_bwd_soft.  The template's weight is the Function's one
+    differentiable input, so autograd itself adds the (n_slots, H) gradient the backward writes whole to ``weight.grad`` across
+    micro-steps; no flat gradient buffer, no zero launch, no bucket callbacks."""
+
+    @staticmethod
+    def forward(ctx, tmpl, eng, tensors, drop):
+        ctx.eng = eng
+        st = _state(eng)
+        ids, seg, mask, pos, feats, mpos, labels, rseq = tensors
+        B, Lt = ids.shape
+        R = int(rseq.numel()) if rseq is not None else 0
+        Li = feats.size(1) if feats is not None else 0
+        m, _ = eng.descriptor(train=True)
+        dev = eng.flat.device
+        loss_acc = torch.empty(3, device=dev, dtype=torch.float32)
+        logits = torch.empty((R if R else B, eng.cfg.vocab_size), device=dev, dtype=torch.float32)
+        o = L.Outputs(logits=logits.data_ptr(), loss=loss_acc.data_ptr(), loss_mean=loss_acc.data_ptr() + 8)
+        bt = L.Batch(B=B, Lt=Lt, Li=Li, input_ids=ids.data_ptr(), token_type=L.ptr(seg), position_ids=L.ptr(pos),
+                     attn_mask=L.ptr(mask), img_feats=L.ptr(feats), mask_pos=L.ptr(mpos), labels=labels.data_ptr(),
+                     n_rows=R, row_seq=L.ptr(rseq), mask_3d=1 if (mask is not None and mask.dim() == 3) else 0)
+        ws = st.workspace(B, Lt, Li, R)
+        soft = eng.soft_template()
+        L.check(L.lib().cpt_train_fwd_soft(C.byref(m), C.byref(soft), C.byref(bt), C.byref(o), ws.data_ptr(), ws.numel(), L.stream_ptr(),
+                                           L.NULL_CB, None, C.byref(drop) if drop is not None else None), "cpt_train_fwd_soft")
+        st.gen += 1
+        ctx.gen = st.gen
+        st.saved = (bt, tensors, st.gen, drop)
+        st.saved_rel2 = (None, None)
+        ctx.tmpl_version = tmpl._version
+        ctx.mark_non_differentiable(logits)
+        ctx.set_materialize_grads(False)
+        return loss_acc[2], logits
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_logits):
+        eng = ctx.eng
+        st = _state(eng)
+        if st.saved is None:
+            raise RuntimeError("cpt_amd: backward called twice (activations of the training forward were released)")
+        bt, tensors, gen, drop = st.saved
+        if gen != ctx.gen:
+            raise RuntimeError("cpt_amd: backward of a stale training forward: the engine keeps the activations of the LATEST "
+                               "training forward only (one workspace per model); call backward() before the next "
+                               "training forward of the same model")
+        from .soft_prompt import template_of
+        tmpl = template_of(eng.module)
+        if tmpl is None or tmpl._version != ctx.tmpl_version:
+            raise RuntimeError("cpt_amd: the soft template was detached or written between the training forward and its backward")
+        m, _ = eng.descriptor(train=True)
+        g = torch.empty_like(tmpl)          # written whole by the backward
+        soft = eng.soft_template(grad=g)
+        gl = grad_loss.to(torch.float32).contiguous()
+        L.check(L.lib().cpt_train_bwd_soft(C.byref(m), C.byref(soft), C.byref(bt), 1.0, gl.data_ptr(), st.ws.data_ptr(), st.ws.numel(),
+                                           L.stream_ptr(), C.byref(drop) if drop is not None else None), "cpt_train_bwd_soft")
+        st.saved = None
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            # data parallel: ONE averaging all-reduce of the (n_slots, H) gradient (63 KB at 21 x 768) -- no buckets, no side stream
+            dist.all_reduce(g)
+            g.div_(dist.get_world_size())
+        return g, None, None, None
+
+
+def _soft_loss_with_grad(model, eng, tensors):
+    if eng.head != "cpt":
+        raise NotImplementedError("cpt_amd: the frozen soft-template step runs on REC_MLM_CPT (head 'cpt'), not head '%s'" % eng.head)
+    from .soft_prompt import template_of
+    st = _state(eng)
+    return _SoftTemplateLoss.apply(template_of(model), eng, tensors, dropout_for(model, st))
+
+
 def mlm_loss_with_grad(model, input_ids, token_type_ids, attention_mask, labels, position_ids, img_feats, mask_token_pos, row_seq=None,
                        rel2=None):
     """(loss, prediction_scores) with autograd history, as REC_MLM_CPT.forward returns them
@@ -301,8 +373,16 @@ def mlm_loss_with_grad(model, input_ids, token_type_ids, attention_mask, labels,
     eng.ensure_packed()
     if eng.pending is None:          # (data parallel: a pending parameter all-gather is awaited bucket by bucket in the forward)
         eng.refresh_shadow(train=True)
+    from .soft_prompt import frozen_step, template_of
+    soft = frozen_step(model)          # (raises for a trainable template beside a trainable backbone)
+    if not soft and template_of(model) is not None:
+        raise NotImplementedError("cpt_amd: training the backbone of a model with a soft template attached is not implemented (the full "
+                                  "backward knows nothing of the substituted rows): detach the template or train it alone")
+    if soft and rel2 is not None:
+        raise NotImplementedError("cpt_amd: the frozen soft-template step runs on the MLM head only")
     st = _state(eng)
-    st.ensure()
+    if not soft:
+        st.ensure()
 
     def prep(t, dt, name):
         if t is None:
@@ -317,6 +397,8 @@ def mlm_loss_with_grad(model, input_ids, token_type_ids, attention_mask, labels,
                prep(attention_mask, torch.int64, "attention_mask"), prep(position_ids, torch.int64, "position_ids"),
                prep(img_feats, torch.float32, "img_feats"), prep(mask_token_pos, torch.int64, "mask_token_pos"),
                prep(labels, torch.int64, "labels"), prep(row_seq, torch.int64, "row_seq"))
+    if soft:
+        return _soft_loss_with_grad(model, eng, tensors)
     trigger = getattr(st, "trigger", None)      # one leaf per engine, made once: autograd needs an input that requires grad, backward returns None for it
     if trigger is None or trigger.device != eng.flat.device:
         trigger = st.trigger = torch.zeros((), device=eng.flat.device, requires_grad=True)

@@ -425,6 +425,37 @@ int cpt_train_bwd_rel2(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b
                        const cpt_dropout* drop);
 int cpt_train_zero_grads_rel2(const cpt_model* m, const cpt_rel2* x, const cpt_model_grads* g, int Li, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Soft-template prompt tuning (Oscar/oscar/explore/sgd_to_explore_template.py:26-66 TemplateEmbedding, :389-426 its loop): a trainable
+ * table tmpl [n_slots][H] fp32 whose rows 1 .. n_slots - 1 REPLACE the word-embedding rows of the ids 1 .. n_slots - 1 ([unused0] ..)
+ * in the text-embedding lookup, while the model itself stays fixed.  Added beside ABI 8, no struct changed.
+ *   forward: a text position whose id satisfies 0 < id < n_slots reads its word row from tmpl[id] instead of word_emb[id]; id 0 (padding)
+ *     and ids >= n_slots are untouched, tmpl[0] is never read; everything behind the lookup -- and the tied decoder table -- is unchanged.
+ *     A NULL struct or tmpl == NULL runs the plain entry point.
+ *   cpt_train_bwd_soft: the backward of a FROZEN model -- the data-gradient chain only (head, LayerNorm backwards, data-gradient GEMMs with
+ *     the GELU gradient, attention backward, dropout and residual handling as cpt_train_bwd_ex), no weight-gradient GEMM, no bias /
+ *     LayerNorm / table column sum, nothing on the region side -- ending in the gradient of the template.
+ *     WRITE contract: g_tmpl [n_slots][H] fp32 is WRITTEN WHOLE by every call (previous contents ignored; row 0 and the rows of slots no
+ *     position uses are exactly zero), and NOTHING ELSE outside the workspace is written: there is no cpt_model_grads and no zero launch.
+ *     A caller that accumulates micro-batches adds g_tmpl to its own sum.  Every slot's sum runs over the text rows in row order
+ *     (b * Lt + t) with a fixed association and no float atomics: the same inputs give the same bits.
+ *   MLM head only (one [MASK] row per sequence, or a label grid through n_rows / row_seq): a model without it (the NSP-CPT heads) is
+ *     CPT_ERR_SHAPE.  Workspace: cpt_train_workspace_bytes(_rows), as the plain step.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    const float* tmpl;     /* [n_slots][H] fp32 */
+    float* g_tmpl;         /* cpt_train_bwd_soft: [n_slots][H] fp32, written whole; the other entry points ignore it */
+    int n_slots;           /* >= 2 */
+} cpt_soft_template;
+int cpt_model_fwd_soft(const cpt_model* m, const cpt_soft_template* st, const cpt_batch* b, const cpt_outputs* o, int flags,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int cpt_model_fwd_rows_soft(const cpt_model* m, const cpt_soft_template* st, const cpt_batch* b, const int64_t* cols, int n_cols, float* logits,
+                            float* row_lse, void* workspace, size_t workspace_bytes, void* stream);
+int cpt_train_fwd_soft(const cpt_model* m, const cpt_soft_template* st, const cpt_batch* b, const cpt_outputs* o, void* workspace,
+                       size_t workspace_bytes, void* stream, cpt_bucket_fn before_bucket, void* user, const cpt_dropout* drop);
+int cpt_train_bwd_soft(const cpt_model* m, const cpt_soft_template* st, const cpt_batch* b, float loss_scale, const float* loss_scale_dev,
+                       void* workspace, size_t workspace_bytes, void* stream, const cpt_dropout* drop);
+
 /* torch.optim.AdamW update (fewshot/refcoco_cpt.py:343,249) over flat buffers of n fp32 elements
  * (n % 4 == 0).  code[i]: 0 = no gradient on this path (skipped), 1 = weight decay, 2 = no decay
  * (fewshot/refcoco_cpt.py:320-338).  grad is multiplied by grad_scale first (1/world after a
