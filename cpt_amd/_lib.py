@@ -103,6 +103,8 @@ _SIGS = {
     "cpt_grad_clip": (C.c_int, [vp, C.c_size_t, C.c_float, vp, vp, vp, C.c_size_t, vp]),
     "cpt_batch_extents": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
     "cpt_trim_batch": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "cpt_train_extents": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
+    "cpt_trim_batch_labels": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "cpt_train_fwd_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(Batch), C.POINTER(Outputs), vp, C.c_size_t, vp, BUCKET_CB, vp,
                                      C.POINTER(Dropout)]),
     "cpt_train_bwd_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(Batch), C.POINTER(ModelGrads), C.c_float, vp, vp, C.c_size_t, vp,

@@ -1,5 +1,5 @@
 """Length-aware evaluation, host side: how far a padded batch is attended to, trimming it, walking a data set by length and packing
-whole queries into batches.  Pure numpy / python (torch CPU tensors are accepted wherever an array is): nothing here touches the GPU.
+whole queries into batches; for training, the extent of a mask with its label grid and the cut of that grid.  Pure numpy / python (torch CPU tensors are accepted wherever an array is): nothing here touches the GPU.
 
 The collate functions pad every sequence to a fixed shape (RefCOCO 70 + 50, GQA / VCR 165 + 45) because eager PyTorch needs rectangular
 tensors.  A position whose attention-mask column is 0 in EVERY sequence of a batch is never a key, and its own row is read by no head-row
@@ -71,6 +71,33 @@ def trim(batch, Lt2, Li2):
         import torch
         out["attention_mask"] = torch.cat(parts, 1)
     return out
+
+
+def label_extent(attention_mask, Lt, label_grid=None):
+    """(Lt', Li') of a training batch: ``batch_extent`` of the (B, Lt + Li) mask, widened so that every labelled position of the (B, Lt + Li)
+    ``label_grid`` (-1 = no label: drivers.gqa_label_grid, vg_label_grid, _label_grid) stays -- a labelled column is a head-row position of
+    ``batch_extent``: Lt' > every labelled text position, a labelled region column keeps the text whole.  Without a grid (the relation heads
+    read [CLS] only) the extent comes from the mask alone.  The device counterpart is cpt_train_extents."""
+    m = np.asarray(attention_mask)
+    if label_grid is None:
+        return batch_extent(m, Lt)
+    g = np.asarray(label_grid)
+    if g.shape != m.shape:
+        raise ValueError("label_extent: the label grid is %s, the mask %s" % (g.shape, m.shape))
+    return batch_extent(m, Lt, np.unique(np.nonzero(g != -1)[1]))
+
+
+def trim_grid(label_grid, Lt, Lt2, Li2):
+    """The (B, Lt + Li) label grid cut as ``trim`` cuts the mask: text columns [0, Lt') then region columns [Lt, Lt + Li') -> (B, Lt' + Li').
+    An array or a CPU tensor."""
+    Li = label_grid.shape[1] - Lt
+    if not (1 <= Lt2 <= Lt and 0 <= Li2 <= Li):
+        raise ValueError("trim_grid: (%d, %d) does not fit the padded (%d, %d)" % (Lt2, Li2, Lt, Li))
+    parts = (label_grid[:, :Lt2], label_grid[:, Lt:Lt + Li2])
+    if isinstance(label_grid, np.ndarray):
+        return np.concatenate(parts, 1)
+    import torch
+    return torch.cat(parts, 1)
 
 
 def length_order(text_len, regions):

@@ -1127,4 +1127,25 @@ int cpt_trim_batch(const int64_t* input_ids, const int64_t* token_type, const in
                                      token_type_out, position_ids_out, attn_mask_out, img_feats_out, (hipStream_t)stream), "cpt_trim_batch");
 }
 
+int cpt_train_extents(const int64_t* mask, int B, int Lt, int Li, const int64_t* label_grid, const int64_t* positions, int n_pos, int32_t* out,
+                      void* stream) {
+    if (!mask || !out || (n_pos > 0 && !positions)) return abi_fail(CPT_ERR_NULL, "cpt_train_extents: null argument");
+    if (B <= 0 || Lt <= 0 || Li < 0 || n_pos < 0) return abi_fail(CPT_ERR_SHAPE, "cpt_train_extents: B %d Lt %d Li %d n_pos %d", B, Lt, Li, n_pos);
+    return abi_check(cpt::train_extents(mask, B, Lt, Li, label_grid, positions, n_pos, out, (hipStream_t)stream), "cpt_train_extents");
+}
+
+int cpt_trim_batch_labels(const int64_t* input_ids, const int64_t* token_type, const int64_t* position_ids, const int64_t* attn_mask,
+                          const float* img_feats, const int64_t* label_grid, int B, int Lt, int Li, int img_dim, int Lt_out, int Li_out,
+                          int64_t* input_ids_out, int64_t* token_type_out, int64_t* position_ids_out, int64_t* attn_mask_out, float* img_feats_out,
+                          int64_t* label_grid_out, void* stream) {
+    if (B <= 0 || Lt <= 0 || Li < 0 || Lt_out <= 0 || Lt_out > Lt || Li_out < 0 || Li_out > Li || (Li_out > 0 && img_dim <= 0))
+        return abi_fail(CPT_ERR_SHAPE, "cpt_trim_batch_labels: B %d, %d + %d -> %d + %d, img_dim %d", B, Lt, Li, Lt_out, Li_out, img_dim);
+    if (!input_ids || !attn_mask || !input_ids_out || !attn_mask_out || (token_type && !token_type_out) || (position_ids && !position_ids_out) ||
+        (Li_out > 0 && (!img_feats || !img_feats_out)) || !label_grid || !label_grid_out)
+        return abi_fail(CPT_ERR_NULL, "cpt_trim_batch_labels: null argument");
+    return abi_check(cpt::trim_batch(input_ids, token_type, position_ids, attn_mask, img_feats, B, Lt, Li, img_dim, Lt_out, Li_out, input_ids_out,
+                                     token_type_out, position_ids_out, attn_mask_out, img_feats_out, (hipStream_t)stream, label_grid, label_grid_out),
+                     "cpt_trim_batch_labels");
+}
+
 }  // extern "C"

@@ -317,6 +317,9 @@ int grad_clip(float* g, size_t n, float max_norm, const double* sq_in, float* ou
 // trim.hip: extents of the attended part of a padded batch and its contiguous copy (cpt_batch_extents, cpt_trim_batch)
 int batch_extents(const int64_t* mask, int B, int Lt, int Li, const int64_t* mask_pos, int n_pos, int32_t* out, hipStream_t s);
 int trim_batch(const int64_t* ids, const int64_t* type, const int64_t* pos, const int64_t* mask, const float* img, int B, int Lt, int Li, int D,
-               int Lt2, int Li2, int64_t* ids_o, int64_t* type_o, int64_t* pos_o, int64_t* mask_o, float* img_o, hipStream_t s);
+               int Lt2, int Li2, int64_t* ids_o, int64_t* type_o, int64_t* pos_o, int64_t* mask_o, float* img_o, hipStream_t s,
+               const int64_t* lab = nullptr, int64_t* lab_o = nullptr);      // (lab: the label grid of cpt_trim_batch_labels)
+// trim.hip, training: extents of a mask with a label grid or labelled positions, one workgroup and no atomics (cpt_train_extents)
+int train_extents(const int64_t* mask, int B, int Lt, int Li, const int64_t* grid, const int64_t* pos, int n_pos, int32_t* out, hipStream_t s);
 
 }  // namespace cpt

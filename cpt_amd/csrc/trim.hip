@@ -7,7 +7,13 @@
 //   trim_batch:    one launch.  The first workgroups copy the region features: per sequence the Li' x D floats that stay are contiguous
 //                  in the source and in the destination, and with D even (2054) both start on 8-byte boundaries, so they move as
 //                  16-byte accesses declared 8-byte aligned (as pad_cast reads them), a scalar tail behind; four chunks per lane in
-//                  flight before the first store.  The other workgroups copy the int64 rows (ids, token types, position ids, mask).
+//                  flight before the first store.  The other workgroups copy the int64 rows (ids, token types, position ids, mask -- and,
+//                  for cpt_trim_batch_labels, a (B, Lt + Li) label grid cut exactly as the mask is).
+// Length-aware training (cpt_train_extents, cpt_trim_batch_labels):
+//   train_extents: the extents of a mask TOGETHER with what the loss reads: a (B, Lt + Li) label grid (-1 = no label) or a list of labelled
+//                  positions.  ONE workgroup, no memset node and no atomic of any kind: every lane walks the flat mask (and grid) in 16-byte
+//                  reads, consecutive lanes on consecutive addresses along L, a wave reduces by shuffles, the four wave results meet in LDS
+//                  and lane 0 combines them in wave order and stores the two words.  A few-shot training batch is 4 x 210 entries.
 #include "common.h"
 #include "kernels.h"
 
@@ -87,6 +93,65 @@ int batch_extents(const int64_t* mask, int B, int Lt, int Li, const int64_t* mas
     return CPT_OK;
 }
 
+// ---- train_extents ----
+// One workgroup.  flat: the (B, L) array; LABELS: an entry counts when it is != -1 and follows the head-row rule (extent_of_pos), else when it
+// is != 0 and follows the mask rule.  vec: the array is 16-byte aligned.
+template <bool LABELS>
+__device__ __forceinline__ void extent_scan(const int64_t* __restrict__ flat, size_t total, int L, int Lt, int Li, int vec, int& tmax, int& imax) {
+    auto see = [&](size_t idx, long long v) {
+        if (LABELS ? v == -1 : v == 0) return;
+        const int c = (int)(idx % L);
+        if (LABELS) extent_of_pos(c, Lt, Li, tmax, imax);
+        else if (c < Lt) tmax = max(tmax, c + 1);
+        else imax = max(imax, c - Lt + 1);
+    };
+    if (vec) {
+        const i64x2* m2 = reinterpret_cast<const i64x2*>(flat);
+        const size_t n2 = total / 2;
+        for (size_t i = threadIdx.x; i < n2; i += TR_THREADS) {
+            const i64x2 v = m2[i];
+            see(2 * i, v[0]);
+            see(2 * i + 1, v[1]);
+        }
+        if (threadIdx.x == 0 && (total & 1)) see(total - 1, flat[total - 1]);
+    } else {
+        for (size_t i = threadIdx.x; i < total; i += TR_THREADS) see(i, flat[i]);
+    }
+}
+
+__global__ __launch_bounds__(TR_THREADS) void train_extents_kernel(const int64_t* __restrict__ mask, int B, int Lt, int Li,
+                                                                   const int64_t* __restrict__ grid, const int64_t* __restrict__ pos, int n_pos,
+                                                                   int* __restrict__ out, int vec_mask, int vec_grid) {
+    __shared__ int lds[2][TR_THREADS / 64];
+    const int L = Lt + Li;
+    const size_t total = (size_t)B * L;
+    int tmax = 1, imax = 0;                 // (the [CLS] row always stays)
+    extent_scan<false>(mask, total, L, Lt, Li, vec_mask, tmax, imax);
+    if (grid) extent_scan<true>(grid, total, L, Lt, Li, vec_grid, tmax, imax);
+    if (pos)
+        for (int i = threadIdx.x; i < n_pos; i += TR_THREADS) extent_of_pos(pos[i], Lt, Li, tmax, imax);
+    tmax = wave_max_i(tmax);
+    imax = wave_max_i(imax);
+    if ((threadIdx.x & 63) == 0) { lds[0][threadIdx.x >> 6] = tmax; lds[1][threadIdx.x >> 6] = imax; }
+    __syncthreads();
+    if (threadIdx.x == 0) {                 // the fixed-order combine: waves 0, 1, 2, 3
+        int t = lds[0][0], r = lds[1][0];
+#pragma unroll
+        for (int w = 1; w < TR_THREADS / 64; ++w) { t = max(t, lds[0][w]); r = max(r, lds[1][w]); }
+        out[0] = t;
+        out[1] = r;
+    }
+}
+
+int train_extents(const int64_t* mask, int B, int Lt, int Li, const int64_t* grid, const int64_t* pos, int n_pos, int32_t* out, hipStream_t s) {
+    if (B <= 0 || Lt <= 0 || Li < 0 || n_pos < 0) return CPT_ERR_SHAPE;
+    if (!mask || !out || (n_pos > 0 && !pos)) return CPT_ERR_NULL;
+    if ((uintptr_t)mask % 8 || (grid && (uintptr_t)grid % 8) || (uintptr_t)out % 4) return CPT_ERR_ALIGN;
+    train_extents_kernel<<<dim3(1), dim3(TR_THREADS), 0, s>>>(mask, B, Lt, Li, grid, n_pos > 0 ? pos : nullptr, n_pos, out,
+                                                              ((uintptr_t)mask % 16) == 0, grid && ((uintptr_t)grid % 16) == 0);
+    return CPT_OK;
+}
+
 // ---- trim_batch ----
 constexpr int TB_UNR = 4;
 
@@ -95,6 +160,8 @@ struct TrimArgs {
     const float* img;
     int64_t *ids_o, *type_o, *pos_o, *mask_o;
     float* img_o;
+    const int64_t* grid;                     // optional (B, Lt + Li) label grid, cut as the mask is (cpt_trim_batch_labels)
+    int64_t* grid_o;
     int B, Lt, Li, D, Lt2, Li2;
     unsigned nfeat;                          // workgroups [0, nfeat) copy the region features, the others the int64 rows
 };
@@ -156,7 +223,9 @@ __device__ __forceinline__ void trim_rows_block(const TrimArgs& a, unsigned bloc
         } else {
             const size_t j = idx - n_text, b = j / L2;
             const int c = (int)(j % L2);
-            a.mask_o[j] = a.mask[b * (a.Lt + a.Li) + (c < a.Lt2 ? c : a.Lt + (c - a.Lt2))];
+            const size_t src = b * (a.Lt + a.Li) + (c < a.Lt2 ? c : a.Lt + (c - a.Lt2));
+            a.mask_o[j] = a.mask[src];
+            if (a.grid) a.grid_o[j] = a.grid[src];
         }
     }
 }
@@ -168,9 +237,11 @@ __global__ __launch_bounds__(TR_THREADS) void trim_batch_kernel(TrimArgs a) {
 }
 
 int trim_batch(const int64_t* ids, const int64_t* type, const int64_t* pos, const int64_t* mask, const float* img, int B, int Lt, int Li, int D,
-               int Lt2, int Li2, int64_t* ids_o, int64_t* type_o, int64_t* pos_o, int64_t* mask_o, float* img_o, hipStream_t s) {
+               int Lt2, int Li2, int64_t* ids_o, int64_t* type_o, int64_t* pos_o, int64_t* mask_o, float* img_o, hipStream_t s,
+               const int64_t* lab, int64_t* lab_o) {
     if (B <= 0 || Lt <= 0 || Li < 0 || Lt2 <= 0 || Lt2 > Lt || Li2 < 0 || Li2 > Li || (Li2 > 0 && D <= 0)) return CPT_ERR_SHAPE;
-    if (!ids || !mask || !ids_o || !mask_o || (type && !type_o) || (pos && !pos_o) || (Li2 > 0 && (!img || !img_o))) return CPT_ERR_NULL;
+    if (!ids || !mask || !ids_o || !mask_o || (type && !type_o) || (pos && !pos_o) || (Li2 > 0 && (!img || !img_o)) || (lab && !lab_o))
+        return CPT_ERR_NULL;
     const size_t seg = (size_t)Li2 * D;
     const bool vec = seg > 0 && D % 2 == 0 && ((uintptr_t)img % 8) == 0 && ((uintptr_t)img_o % 8) == 0;
     const size_t work = seg == 0 ? 0 : (vec ? (size_t)B * ((seg + 3) / 4) : (size_t)B * seg);
@@ -181,7 +252,7 @@ int trim_batch(const int64_t* ids, const int64_t* type, const int64_t* pos, cons
     const size_t rows = (size_t)B * Lt2 + (size_t)B * (Lt2 + Li2);
     size_t nrow = (rows + (size_t)TR_THREADS * 4 - 1) / ((size_t)TR_THREADS * 4);
     nrow = nrow < 1 ? 1 : (nrow > 1024 ? 1024 : nrow);
-    TrimArgs a{ids, type, pos, mask, img, ids_o, type_o, pos_o, mask_o, img_o, B, Lt, Li, D, Lt2, Li2, (unsigned)nfeat};
+    TrimArgs a{ids, type, pos, mask, img, ids_o, type_o, pos_o, mask_o, img_o, lab, lab ? lab_o : nullptr, B, Lt, Li, D, Lt2, Li2, (unsigned)nfeat};
     const dim3 grid((unsigned)(nfeat + nrow)), block(TR_THREADS);
     if (vec) trim_batch_kernel<true><<<grid, block, 0, s>>>(a);
     else trim_batch_kernel<false><<<grid, block, 0, s>>>(a);

@@ -31,6 +31,11 @@ logger = logging.getLogger(__name__)
 #           PCIe bytes); the encoder then runs on (B, Lt' + Li').  Head-row outputs only, which is all these drivers read.
 #   bucket  each rank walks ITS shard by ascending length (batching.length_order; an item of several sequences -- a query, a VCR question, a VG
 #           pair -- stays whole and counts by its longest sequence) and writes every result back at the item's own index.
+#   Length-aware training: the six training loops below take trim=False too.  With trim=True the label grid of each micro-batch is built on the
+#   host, the extent comes from the mask AND the grid (batching.label_extent: every labelled position stays; the relation heads' extent from the
+#   mask alone, both Q->AR blocks sharing one), and the host arrays and the grid are cut before the H2D copy: no device work, no synchronisation.
+#   The trimmed rows contribute exact zeros to the loss's gradient, so only the order of the sums changes; with dropout on, the masks are drawn
+#   for the shape that runs, so a trimmed step draws other masks than the padded one would (README "Length-aware training").
 def _item_length(mask, Lt):
     """The length key of one item: text_len + regions of its longest sequence."""
     t, r = batching.extents(mask, Lt)
@@ -90,6 +95,13 @@ def _trim_host(b, head_pos=None):
     """batching.trim of a host batch to its own batch extent -> (batch, Li')."""
     lt, li = batching.batch_extent(b["attention_mask"], b["input_ids"].shape[1], head_pos)
     return batching.trim(b, lt, li), li
+
+
+def _trim_train_host(host, grid):
+    """A host batch (CPU tensors) and its (B, Lt + Li) label grid, both cut to batching.label_extent of the two."""
+    Lt = host["input_ids"].shape[1]
+    lt, li = batching.label_extent(host["attention_mask"], Lt, grid)
+    return batching.trim(host, lt, li), batching.trim_grid(grid, Lt, lt, li)
 
 
 def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4, colour_columns_only=True, trim=False, bucket=False,
@@ -163,19 +175,32 @@ def _apply_lr(optimizer, lr, head_multiplier):
         g["lr"] = lr
 
 
-def _scheduled_pass(model, optimizer, batches, opts, device, global_step, grid_fn):
+def _device_batch(host_batch, grid_fn, device, trim):
+    """(batch on the device, its label grid on the device).  trim: the grid is built on the host and both are cut there first."""
+    if not trim:
+        batch = {name: torch.as_tensor(t).to(device) for name, t in host_batch.items()}
+        return batch, grid_fn(batch)
+    host = {name: torch.as_tensor(t) for name, t in host_batch.items()}
+    host, grid = _trim_train_host(host, grid_fn(host))
+    batch = {name: t.to(device) for name, t in host.items()}
+    if batch.get("img_feats") is not None and batch["img_feats"].size(1) == 0:
+        batch["img_feats"] = None          # Li' = 0: the step runs text-only, as it does without regions
+    return batch, grid.to(device)
+
+
+def _scheduled_pass(model, optimizer, batches, opts, device, global_step, grid_fn, trim=False):
     """The loop train_batch and train_vg_batch share: per batch the scheduled learning rate, then zero_grad / forward with
     masked_lm_labels=grid_fn(batch) / backward / step; a step that raises RuntimeError is logged and skipped without advancing the schedule.
     Returns (global_step, [loss tensors])."""
     model.train()
     losses = []
     for index, host_batch in enumerate(batches):
-        batch = {name: torch.as_tensor(t).to(device) for name, t in host_batch.items()}
+        batch, grid = _device_batch(host_batch, grid_fn, device, trim)
         _apply_lr(optimizer, get_lr_sched(global_step, opts), getattr(opts, "lr_mul", 1.0))
         try:
             optimizer.zero_grad()
             loss = model(batch["input_ids"], batch["segment_ids"], batch["attention_mask"], img_feats=batch["img_feats"],
-                         masked_lm_labels=grid_fn(batch))[0]
+                         masked_lm_labels=grid)[0]
             loss.backward()
             optimizer.step()
         except RuntimeError as err:
@@ -186,27 +211,28 @@ def _scheduled_pass(model, optimizer, batches, opts, device, global_step, grid_f
     return global_step, losses
 
 
-def train_batch(model, optimizer, batches, opts, device, global_step=0):
+def train_batch(model, optimizer, batches, opts, device, global_step=0, trim=False):
     """One pass over ``batches`` (dicts with img_feats, input_ids, attention_mask, segment_ids, mask_token_pos, colors): the few-shot
     step of fewshot/refcoco_cpt.py:225-255 -- label grid, scheduled learning rate, zero_grad / forward / backward / step; a step that
-    raises RuntimeError is logged and skipped without advancing the schedule (_scheduled_pass).  Returns (global_step, [loss tensors])."""
-    return _scheduled_pass(model, optimizer, batches, opts, device, global_step, _label_grid)
+    raises RuntimeError is logged and skipped without advancing the schedule (_scheduled_pass).  Returns (global_step, [loss tensors]).
+    trim: length-aware training, see the top of this module."""
+    return _scheduled_pass(model, optimizer, batches, opts, device, global_step, _label_grid, trim)
 
 
-def tune_soft_template(model, optimizer, batches, device):
+def tune_soft_template(model, optimizer, batches, device, trim=False):
     """The template-tuning loop of explore/sgd_to_explore_template.py:396-412 on a model with a soft template attached
     (cpt_amd/soft_prompt.py attach; ``optimizer`` is any torch optimizer over that one tensor -- the reference builds
     ``AdamW([template], lr=0.02, eps=1e-8)``): per batch the label grid with the colour id at the [MASK] position, the loss divided
     ADDITIONALLY by the batch size (:409), zero_grad / backward / step.  Returns the list of (divided) loss tensors.
     The reference runs this loop on BertImgForPreTraining with next_sentence_label=0, so its loss also carries the contrastive term;
-    here it is REC_MLM_CPT's MLM loss alone."""
+    here it is REC_MLM_CPT's MLM loss alone.  trim: length-aware training, see the top of this module."""
     model.train()
     losses = []
     for host_batch in batches:
-        batch = {name: torch.as_tensor(t).to(device) for name, t in host_batch.items()}
+        batch, grid = _device_batch(host_batch, _label_grid, device, trim)
         optimizer.zero_grad()
         loss = model(batch["input_ids"], batch["segment_ids"], batch["attention_mask"], img_feats=batch["img_feats"],
-                     masked_lm_labels=_label_grid(batch))[0]
+                     masked_lm_labels=grid)[0]
         loss = loss / batch["input_ids"].size(0)
         loss.backward()
         optimizer.step()
@@ -273,13 +299,13 @@ def vg_schedule(opts, num_train_epochs):
     return opts
 
 
-def train_vg_batch(model, optimizer, batches, opts, device, global_step=0):
+def train_vg_batch(model, optimizer, batches, opts, device, global_step=0, trim=False):
     """One pass of vg_cpt.py:217-252 (train_batch) over ``batches``: dicts with img_feats, input_ids, attention_mask, segment_ids,
     mask_token_pos (n, 2) (sequence, position) and row_labels (n,) -- prompts.assemble_vg_train rows concatenated, 6 labelled rows per
     pair.  The label grid holds several labelled positions per sequence (the multi-row training path of REC_MLM_CPT.forward); LR
     schedule (opts from vg_schedule), zero_grad / forward / backward / step and the skipped-step rule as train_batch (_scheduled_pass).
-    Returns (global_step, [loss tensors])."""
-    return _scheduled_pass(model, optimizer, batches, opts, device, global_step, vg_label_grid)
+    Returns (global_step, [loss tensors]).  trim: length-aware training, see the top of this module."""
+    return _scheduled_pass(model, optimizer, batches, opts, device, global_step, vg_label_grid, trim)
 
 
 # ---- VCR Q->AR (Oscar/oscar/fewshot/vcr_qar_nsp_cpt.py; launched by cmds/vcr/qar_cpt_fsl.sh) ----------------------------------------------
@@ -358,19 +384,20 @@ def qar_accumulation(n_examples, per_gpu_train_batch_size, world_size, n_batches
 gqa_accumulation = qar_accumulation
 
 
-def train_vcr_qar_batch(model, optimizer, scheduler, batches, opts, device, global_step=0):
+def train_vcr_qar_batch(model, optimizer, scheduler, batches, opts, device, global_step=0, trim=False):
     """One epoch of vcr_qar_nsp_cpt.py:453-525 over ``batches`` (lists of prompts.assemble_vcr_qar dicts with img_feats, one list per micro-step):
     class-0 labels of both blocks (qar_choice_labels), loss = q_a_loss + qa_r_loss from ONE encoder pass (qar_forward), divided by
     opts.gradient_accumulation_steps when that is > 1, backward, torch.nn.utils.clip_grad_norm_(model.parameters(), opts.max_grad_norm) on EVERY
     micro-step (in place on the accumulated gradient, as the reference), and every gradient_accumulation_steps micro-steps scheduler.step() BEFORE
     optimizer.step(), then model.zero_grad() (_accumulate, with the host clip).  Micro-steps that do not complete a window take no optimizer step
-    and their gradient is kept (the reference zeroes only after a step).  Returns (global_step, [loss tensors, as divided])."""
+    and their gradient is kept (the reference zeroes only after a step).  Returns (global_step, [loss tensors, as divided]).
+    trim: length-aware training (both blocks of a micro-step cut to ONE extent, _qar_blocks), see the top of this module."""
     model.train()
 
     def micro():
         for chunk in batches:
             n_ans, n_rats = _qar_layout(chunk)
-            qa, qr = _qar_blocks(chunk, device)
+            qa, qr = _qar_blocks(chunk, device, trim)
             la, lr_ = scoring.qar_choice_labels([q["label"][0] for q in chunk], [q["label"][1] for q in chunk], n_ans, n_rats)
             yield model.qar_forward(qa, qr, la, lr_)[0]
     global_step, losses, _ = _accumulate(model, optimizer, scheduler, micro(), opts, global_step, use_device_clip=False)
@@ -476,24 +503,30 @@ def _accumulate(model, optimizer, scheduler, micro_losses, opts, global_step, us
     return global_step, losses, norms
 
 
-def train_gqa_batch(model, optimizer, scheduler, batches, opts, device, label_token_ids, global_step=0, use_device_clip=None):
+def train_gqa_batch(model, optimizer, scheduler, batches, opts, device, label_token_ids, global_step=0, use_device_clip=None, trim=False):
     """One epoch of gqa_cpt.py:423-462 over ``batches``: dicts with input_ids (B, Lt), attention_mask (B, Lt + Li), segment_ids, img_feats
     (B, Li, D) and label_id (B,) or (B, 1).  Label grid of gqa_label_grid, loss / gradient_accumulation_steps, backward and clip on every
     micro-step, scheduler before optimizer, model.zero_grad() after (_accumulate).  use_device_clip: None = optimizer.clip_grad_norm_device when
-    the optimizer has it, False = torch.nn.utils.clip_grad_norm_.  Returns (global_step, [loss tensors, as divided])."""
-    global_step, losses, _ = _gqa_pass(model, optimizer, scheduler, batches, opts, device, label_token_ids, global_step, use_device_clip)
+    the optimizer has it, False = torch.nn.utils.clip_grad_norm_.  Returns (global_step, [loss tensors, as divided]).
+    trim: length-aware training, see the top of this module."""
+    global_step, losses, _ = _gqa_pass(model, optimizer, scheduler, batches, opts, device, label_token_ids, global_step, use_device_clip, trim)
     return global_step, losses
 
 
-def _gqa_pass(model, optimizer, scheduler, batches, opts, device, label_token_ids, global_step, use_device_clip):
+def _gqa_pass(model, optimizer, scheduler, batches, opts, device, label_token_ids, global_step, use_device_clip, trim=False):
     model.train()
-    label_token_ids = torch.as_tensor(label_token_ids, dtype=torch.long).to(device)
+    # the label grid is built where the batch is when grid_fn runs (_device_batch): on the host with trim, on the device without -- the token
+    # table the lambda below closes over lives on that side
+    label_token_ids = torch.as_tensor(label_token_ids, dtype=torch.long)
+    if not trim:
+        label_token_ids = label_token_ids.to(device)
 
     def micro():
         for host_batch in batches:
-            b = {k: torch.as_tensor(v).to(device) for k, v in host_batch.items()}
-            grid = gqa_label_grid(b["input_ids"], b["attention_mask"], b["label_id"], label_token_ids)
-            yield model(b["input_ids"], b["segment_ids"], b["attention_mask"], img_feats=b["img_feats"].float(), masked_lm_labels=grid)[0]
+            b, grid = _device_batch(host_batch, lambda x: gqa_label_grid(x["input_ids"], x["attention_mask"], x["label_id"], label_token_ids),
+                                    device, trim)
+            yield model(b["input_ids"], b["segment_ids"], b["attention_mask"], img_feats=None if b["img_feats"] is None else b["img_feats"].float(),
+                        masked_lm_labels=grid)[0]
     return _accumulate(model, optimizer, scheduler, micro(), opts, global_step, use_device_clip)
 
 
@@ -550,22 +583,23 @@ def val_vcr(model, questions, device, batch_questions=8, trim=False, bucket=Fals
     return {"preds": preds, "correct": correct, "scores": scores, "q_ids": q_ids, "acc": acc}
 
 
-def train_vcr_batch(model, optimizer, scheduler, batches, opts, device, global_step=0, use_device_clip=None):
+def train_vcr_batch(model, optimizer, scheduler, batches, opts, device, global_step=0, use_device_clip=None, trim=False):
     """One epoch of vcr_nsp_cpt.py:430-473 over ``batches`` (lists of prompts.assemble_vcr dicts with img_feats, one list per micro-step, one
     ``interval`` per pass): class 0 at each question's correct choice and 1 elsewhere (scoring.nsp_choice_labels), the NSP loss, and the
-    accumulation loop of train_gqa_batch (_accumulate).  Returns (global_step, [loss tensors, as divided])."""
-    global_step, losses, _ = _vcr_pass(model, optimizer, scheduler, batches, opts, device, global_step, use_device_clip)
+    accumulation loop of train_gqa_batch (_accumulate).  Returns (global_step, [loss tensors, as divided]).
+    trim: length-aware training (the extent from the mask alone: the loss reads [CLS]), see the top of this module."""
+    global_step, losses, _ = _vcr_pass(model, optimizer, scheduler, batches, opts, device, global_step, use_device_clip, trim)
     return global_step, losses
 
 
-def _vcr_pass(model, optimizer, scheduler, batches, opts, device, global_step, use_device_clip):
+def _vcr_pass(model, optimizer, scheduler, batches, opts, device, global_step, use_device_clip, trim=False):
     model.train()
     batches = list(batches)
     interval = batches[0][0]["input_ids"].shape[0] if batches else 0
 
     def micro():
         for chunk in batches:
-            b, iv = _vcr_block(chunk, device)
+            b, iv = _vcr_block(chunk, device, trim)
             if iv != interval:
                 raise ValueError("VCR Q->A: one interval per pass (got %d after %d)" % (iv, interval))
             cls_labels = scoring.nsp_choice_labels([_vcr_label(q) for q in chunk], interval, len(chunk) * interval, device)

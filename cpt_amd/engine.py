@@ -91,6 +91,7 @@ class PackedModel(object):
         self._fold_stale = True
         self.pending = None         # data-parallel optimizer whose parameter all-gather is still in flight (train.FusedAdamW)
         self.last_shape = None      # (B, Lt, Li) the last inference forward ran on: the padded shape, or what trim=True cut it to
+        self.last_train_shape = None    # (B, Lt, Li) the last training forward ran on (train.py; cut by a driver's trim=True or model.trim_training)
 
     # ---- packing -------------------------------------------------------------------------
     def _named(self):

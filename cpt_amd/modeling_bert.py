@@ -110,6 +110,11 @@ class _EngineMixin(object):
     # the part of the padded batch some sequence attends to (PackedModel.forward trim=True: one small synchronisation per forward; skipped for
     # outputs that return every position, 3-D masks, losses and training).  A reference-style loop gets it by setting this one attribute.
     trim_padding = False
+    # Length-aware training (extension; README "Length-aware training"): True makes every training forward of this model (REC_MLM_CPT, NSPCPT,
+    # VCRQAR_NSPCPT.qar_forward / forward, the frozen soft-template step) cut its padded device batch to the part some sequence attends to or the
+    # loss reads (train.trim_training_batch: one small synchronisation per training forward; skipped with a 3-D mask or without a mask).  Separate
+    # from trim_padding, which never touches a training forward.
+    trim_training = False
 
     def _engine(self):
         eng = self.__dict__.get("_cpt_engine")

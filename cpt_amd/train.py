@@ -114,6 +114,8 @@ class _TrainState(object):
             self.gdesc = (g, layers)
 
     def workspace(self, B, Lt, Li, n_rows=0):
+        """The step's workspace for the shape that RUNS.  Grow-only: a smaller shape behind a larger one (length-aware training: every micro-step
+        may run another (B, Lt' + Li')) keeps the larger allocation, so its address stays put and nothing is freed under a running stream."""
         eng = self.eng
         m, _ = eng.descriptor(train=True)
         need = L.lib().cpt_train_workspace_bytes_rows(C.byref(m.dims), B, Lt, Li, n_rows)
@@ -182,6 +184,7 @@ class _MLMLoss(torch.autograd.Function):
             # per engine, so this forward overwrites them (their backward will raise instead of using the wrong ones)
             pass
         ws = st.workspace(B, Lt, Li, R)
+        eng.last_train_shape = (B, Lt, Li)
         errs = []
 
         def before_bucket(_user, k):
@@ -302,6 +305,7 @@ class _SoftTemplateLoss(torch.autograd.Function):
                      attn_mask=L.ptr(mask), img_feats=L.ptr(feats), mask_pos=L.ptr(mpos), labels=labels.data_ptr(),
                      n_rows=R, row_seq=L.ptr(rseq), mask_3d=1 if (mask is not None and mask.dim() == 3) else 0)
         ws = st.workspace(B, Lt, Li, R)
+        eng.last_train_shape = (B, Lt, Li)
         soft = eng.soft_template()
         L.check(L.lib().cpt_train_fwd_soft(C.byref(m), C.byref(soft), C.byref(bt), C.byref(o), ws.data_ptr(), ws.numel(), L.stream_ptr(),
                                            L.NULL_CB, None, C.byref(drop) if drop is not None else None), "cpt_train_fwd_soft")
@@ -344,6 +348,52 @@ class _SoftTemplateLoss(torch.autograd.Function):
         return g, None, None, None
 
 
+def trim_training_batch(eng, input_ids, token_type_ids, attention_mask, position_ids, img_feats, label_grid=None, positions=None):
+    """``model.trim_training`` on a padded DEVICE batch: cut it to the part some sequence attends to or the loss reads, for a training step.
+    One launch computes {Lt', Li'} from the 2-D mask and either the (B, Lt + Li) ``label_grid`` (-1 = no label) or the labelled ``positions``
+    (mask_token_pos / the position list that goes with row_seq), or neither for the relation heads (include/cpt_hip.h cpt_train_extents); the
+    two int32 are read back -- ONE small synchronisation of the current stream per training forward; a loop that cannot afford it trims on the
+    host before its copy, as the drivers do with trim=True -- and one launch copies what stays (cpt_trim_batch / cpt_trim_batch_labels).
+    Labelled positions need no remapping: a labelled text column p gives Lt' > p and text columns keep their indices; a labelled region column
+    keeps the text whole.  Returns (input_ids, token_type_ids, attention_mask, position_ids, img_feats, label_grid), on (B, Lt' + Li').
+    Returned as they came: a 3-D mask, no mask, or a batch attended (or labelled) to its last column."""
+    same = (input_ids, token_type_ids, attention_mask, position_ids, img_feats, label_grid)
+    if attention_mask is None or attention_mask.dim() != 2 or not input_ids.is_cuda:
+        return same
+    i64 = lambda t: None if t is None else t.to(torch.int64).contiguous()
+    ids, tt, mask, pos_ids = i64(input_ids), i64(token_type_ids), i64(attention_mask), i64(position_ids)
+    grid = i64(label_grid)
+    positions = None if positions is None else i64(positions).reshape(-1)
+    feats = None if img_feats is None else img_feats.to(torch.float32).contiguous()
+    B, Lt = ids.shape
+    Li = feats.size(1) if feats is not None else 0
+    if tuple(mask.shape) != (B, Lt + Li) or (grid is not None and tuple(grid.shape) != (B, Lt + Li)):
+        return same                       # (the training step itself reports the mismatch)
+    dev = ids.device
+    st = L.stream_ptr()
+    ext = eng._buffer("train_ext", 2, zero=True, dtype=torch.int32, device=dev)
+    L.check(L.lib().cpt_train_extents(mask.data_ptr(), B, Lt, Li, L.ptr(grid), L.ptr(positions), positions.numel() if positions is not None else 0,
+                                      ext.data_ptr(), st), "cpt_train_extents")
+    lt2, li2 = ext.tolist()               # the synchronisation
+    # every labelled position is < Lt' or the text is whole (the rule of the launch): positions index the trimmed batch as they are
+    assert 1 <= lt2 <= Lt and 0 <= li2 <= Li, (lt2, li2, Lt, Li)
+    if (lt2, li2) == (Lt, Li):
+        return same
+    new = lambda t, *shape: None if t is None else torch.empty(shape, device=dev, dtype=t.dtype)
+    ids2, tt2, pos2 = new(ids, B, lt2), new(tt, B, lt2), new(pos_ids, B, lt2)
+    mask2, grid2 = new(mask, B, lt2 + li2), new(grid, B, lt2 + li2)
+    feats2 = new(feats, B, li2, feats.size(2)) if li2 > 0 else None
+    D = feats.size(2) if feats is not None else 0
+    if grid is not None:
+        L.check(L.lib().cpt_trim_batch_labels(ids.data_ptr(), L.ptr(tt), L.ptr(pos_ids), mask.data_ptr(), L.ptr(feats), grid.data_ptr(), B, Lt, Li, D,
+                                              lt2, li2, ids2.data_ptr(), L.ptr(tt2), L.ptr(pos2), mask2.data_ptr(), L.ptr(feats2), grid2.data_ptr(), st),
+                "cpt_trim_batch_labels")
+    else:
+        L.check(L.lib().cpt_trim_batch(ids.data_ptr(), L.ptr(tt), L.ptr(pos_ids), mask.data_ptr(), L.ptr(feats), B, Lt, Li, D, lt2, li2,
+                                       ids2.data_ptr(), L.ptr(tt2), L.ptr(pos2), mask2.data_ptr(), L.ptr(feats2), st), "cpt_trim_batch")
+    return ids2, tt2, mask2, pos2, feats2, grid2
+
+
 def _soft_loss_with_grad(model, eng, tensors):
     if eng.head != "cpt":
         raise NotImplementedError("cpt_amd: the frozen soft-template step runs on REC_MLM_CPT (head 'cpt'), not head '%s'" % eng.head)
@@ -353,7 +403,7 @@ def _soft_loss_with_grad(model, eng, tensors):
 
 
 def mlm_loss_with_grad(model, input_ids, token_type_ids, attention_mask, labels, position_ids, img_feats, mask_token_pos, row_seq=None,
-                       rel2=None):
+                       rel2=None, trim=None):
     """(loss, prediction_scores) with autograd history, as REC_MLM_CPT.forward returns them
     (modeling_rec.py:147-152).  ``mask_token_pos`` is required: the loss only sees the [MASK] rows
     (fewshot/refcoco_cpt.py:231-233 puts -1 everywhere else).  For NSPCPT (head "nsp", modeling_vcr.py:115-129)
@@ -361,7 +411,10 @@ def mlm_loss_with_grad(model, input_ids, token_type_ids, attention_mask, labels,
     the (B, num_contrast_classes) relation scores.  ``rel2`` = (B0, host int64 labels or None): VCRQAR_NSPCPT (head "qar"), rows [0, B0)
     through cls_ans and [B0, B) through cls_rat, the loss the sum of the two groups' means (cpt_train_fwd_rel2).
     ``row_seq`` (label grids with any number of labelled positions per sequence): ``labels`` / ``mask_token_pos`` then list the R
-    labelled positions, ``row_seq`` (R,) the sequence each belongs to; the second result is the (R, V) scores of those rows."""
+    labelled positions, ``row_seq`` (R,) the sequence each belongs to; the second result is the (R, V) scores of those rows.
+    ``trim`` (None: ``model.trim_training``): the padded device batch is first cut to the part some sequence attends to or the loss reads
+    (trim_training_batch: one small synchronisation); the step then runs unchanged on (B, Lt' + Li').  ``eng.last_train_shape`` is the
+    (B, Lt', Li') that ran."""
     eng = model._engine()
     if (rel2 is not None) != (eng.head == "qar"):
         raise RuntimeError("cpt_amd: the two-head step (rel2) belongs to the VCR Q->AR model and it alone")
@@ -393,6 +446,9 @@ def mlm_loss_with_grad(model, input_ids, token_type_ids, attention_mask, labels,
 
     if attention_mask is not None and attention_mask.dim() not in (2, 3):
         raise NotImplementedError("cpt_amd: attention_mask must be (B, L) or (B, L, L) (modeling_bert.py:213-218)")
+    if getattr(model, "trim_training", False) if trim is None else trim:
+        input_ids, token_type_ids, attention_mask, position_ids, img_feats, _ = trim_training_batch(
+            eng, input_ids, token_type_ids, attention_mask, position_ids, img_feats, positions=mask_token_pos)
     tensors = (prep(input_ids, torch.int64, "input_ids"), prep(token_type_ids, torch.int64, "token_type_ids"),
                prep(attention_mask, torch.int64, "attention_mask"), prep(position_ids, torch.int64, "position_ids"),
                prep(img_feats, torch.float32, "img_feats"), prep(mask_token_pos, torch.int64, "mask_token_pos"),

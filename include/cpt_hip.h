@@ -308,7 +308,8 @@ int cpt_grad_clip(float* g, size_t n, float max_norm, const double* sq_in, float
 /* ------------------------------------------------------------------------------------------
  * Length-aware evaluation: trim a padded batch to the part any sequence attends to.  Added beside ABI 8, no struct changed.
  * A position whose mask column is 0 in every sequence of the batch is never a key, and its own row is read by no head-row output ([MASK]
- * rows, [CLS] row): dropping it changes only the order of the sums.  Not for outputs that return every position, 3-D masks or training.
+ * rows, [CLS] row): dropping it changes only the order of the sums.  Not for outputs that return every position or 3-D masks; training steps
+ * take the entries further down (cpt_train_extents).
  * ---------------------------------------------------------------------------------------- */
 /* out [2] int32 (device) = {Lt', Li'} of attn_mask [B][Lt + Li] int64 (device): per part (text: columns [0, Lt), regions: [Lt, Lt + Li)) 1 +
  * the last column that is non-zero in any sequence, 0 when there is none -- no prefix form assumed, a hole stays inside.  Lt' >= 1 always.
@@ -323,6 +324,24 @@ int cpt_batch_extents(const int64_t* attn_mask, int B, int Lt, int Li, const int
 int cpt_trim_batch(const int64_t* input_ids, const int64_t* token_type, const int64_t* position_ids, const int64_t* attn_mask, const float* img_feats,
                    int B, int Lt, int Li, int img_dim, int Lt_out, int Li_out, int64_t* input_ids_out, int64_t* token_type_out,
                    int64_t* position_ids_out, int64_t* attn_mask_out, float* img_feats_out, void* stream);
+/* Length-aware TRAINING (added beside ABI 8): the same cut is exact for a training step -- a column no sequence attends to is never a key, no
+ * head row reads its row, so the gradient entering it is exactly zero and it adds exact zeros to every weight gradient, column sum and table
+ * row -- provided every labelled position stays.
+ * cpt_train_extents: out [2] int32 (device) = {Lt', Li'} of attn_mask as cpt_batch_extents defines them, widened by what the loss reads: either
+ * label_grid [B][Lt + Li] int64 (device, optional; -1 = no label, any other entry labels its column) or positions [n_pos] int64 (device, optional:
+ * the mask_pos / (row_seq, position) list of the training step; row_seq is not needed, only the columns count), or neither (relation heads: the
+ * loss reads [CLS] only).  A labelled column follows the head-row rule of cpt_batch_extents: text column p gives Lt' >= p + 1 (so Lt' > every
+ * labelled text position and no position moves), a region column keeps the text whole.  ONE launch of ONE workgroup, no memset node, no atomic:
+ * 16-byte reads along L, wave reductions, one combine in wave order.  Sized for few-shot training batches (4 x 210 entries): the one workgroup
+ * walks all B x (Lt + Li) entries, so the time grows linearly with the batch -- evaluation batches of hundreds of sequences use cpt_batch_extents. */
+int cpt_train_extents(const int64_t* attn_mask, int B, int Lt, int Li, const int64_t* label_grid, const int64_t* positions, int n_pos, int32_t* out,
+                      void* stream);
+/* cpt_trim_batch with a label grid: label_grid_out [B][Lt_out + Li_out] holds text columns [0, Lt_out) and region columns [Lt, Lt + Li_out) of
+ * label_grid [B][Lt + Li], exactly as attn_mask_out is cut from attn_mask (the same copy loop, the same launch). */
+int cpt_trim_batch_labels(const int64_t* input_ids, const int64_t* token_type, const int64_t* position_ids, const int64_t* attn_mask,
+                          const float* img_feats, const int64_t* label_grid, int B, int Lt, int Li, int img_dim, int Lt_out, int Li_out,
+                          int64_t* input_ids_out, int64_t* token_type_out, int64_t* position_ids_out, int64_t* attn_mask_out, float* img_feats_out,
+                          int64_t* label_grid_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Few-shot training step (Oscar/oscar/fewshot/refcoco_cpt.py:231-249): forward that keeps the
