@@ -483,6 +483,17 @@ int cpt_select_regions(const float* mask_logits, int V, const int64_t* color_ids
                                             (hipStream_t)stream), "cpt_select_regions");
 }
 
+int cpt_rec_choose(const float* scores, int S, int V, const int32_t* q_index, int Qb, int Q, const int32_t* seq_first, const int32_t* cols, int C,
+                   const int32_t* cand_first, const double* rects, const double* gt, const uint8_t* has_gt, int none, int divide_by_none,
+                   int32_t* idx, float* score, double* iou, uint8_t* correct, float* cand_score, int32_t* counts, void* stream) {
+    if (!scores || !q_index || !seq_first || !cols || !cand_first || !rects || !gt || !has_gt || !idx || !score || !iou || !correct || !counts)
+        return abi_fail(CPT_ERR_NULL, "cpt_rec_choose: null argument");
+    if (S <= 0 || V <= 0 || Qb <= 0 || Q <= 0 || C <= 0 || none < 0 || none >= V)
+        return abi_fail(CPT_ERR_SHAPE, "cpt_rec_choose: S %d V %d Qb %d Q %d C %d none %d", S, V, Qb, Q, C, none);
+    return abi_check(cpt::rec_choose(scores, S, V, q_index, Qb, Q, seq_first, cols, C, cand_first, rects, gt, has_gt, none, divide_by_none, idx, score,
+                                     iou, correct, cand_score, counts, (hipStream_t)stream), "cpt_rec_choose");
+}
+
 int cpt_argmax_columns(const float* logits, int V, const int64_t* ids, int n_ids, int R, int64_t* out_idx, float* out_val, void* stream) {
     return abi_check(cpt::argmax_columns(logits, V, ids, n_ids, R, out_idx, out_val, (hipStream_t)stream), "cpt_argmax_columns");
 }

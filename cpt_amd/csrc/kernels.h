@@ -314,6 +314,10 @@ int nsp_choose(const float* rel, int n_q, int interval, int n_rel, const int64_t
                hipStream_t s);
 size_t grad_clip_ws_bytes();
 int grad_clip(float* g, size_t n, float max_norm, const double* sq_in, float* out, void* ws, hipStream_t s);
+// rec_eval.hip: RefCOCO REC evaluation -- selection, IoU and accuracy counts of a batch of queries in one launch (cpt_rec_choose)
+int rec_choose(const float* scores, int S, int V, const int32_t* q_index, int Qb, int Q, const int32_t* seq_first, const int32_t* cols, int C,
+               const int32_t* cand_first, const double* rects, const double* gt, const uint8_t* has_gt, int none, int divide_by_none, int32_t* idx,
+               float* score, double* iou, uint8_t* correct, float* cand_score, int* counts, hipStream_t s);
 // trim.hip: extents of the attended part of a padded batch and its contiguous copy (cpt_batch_extents, cpt_trim_batch)
 int batch_extents(const int64_t* mask, int B, int Lt, int Li, const int64_t* mask_pos, int n_pos, int32_t* out, hipStream_t s);
 int trim_batch(const int64_t* ids, const int64_t* type, const int64_t* pos, const int64_t* mask, const float* img, int B, int Lt, int Li, int D,

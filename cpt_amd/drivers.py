@@ -4,6 +4,8 @@
     variant fewshot/refcoco_cpt.py:258-315): per query, score every proposal sequence at its [MASK]
     slot, gather the colour logits, argmax -> chosen rectangle; queries are sharded across ranks and
     the chosen indices are gathered with one fixed-shape all_gather.
+  * ``val_rec``      <- the same two val() functions to their end: selection, IoU against the annotation and
+    the accuracy they return, in one launch per batch against tables uploaded once (cpt_rec_choose).
   * ``train_batch``  <- fewshot/refcoco_cpt.py:225-255: label grid, LR schedule, zero_grad / loss /
     backward / step, RuntimeError per step logged and skipped.
 Datasets, tokeniser and TSV decoding stay outside: a *query* here is already
@@ -67,9 +69,10 @@ def _eval_pass(n_items, groups_of, outputs, step, device, bucket):
     for idx in groups_of(lo, hi):
         with torch.no_grad():
             res = step(idx, lo)
-        sel = _sel(idx, device, bucket)
-        for t, r in zip(local, res):
-            t[sel] = r
+        if local:       # (a step that writes its results itself, at the items' global indices, returns nothing: val_rec)
+            sel = _sel(idx, device, bucket)
+            for t, r in zip(local, res):
+                t[sel] = r
     return tuple(cdist.gather_fixed(t, n_items, fill=o[2]) for t, o in zip(local, outputs))
 
 
@@ -152,6 +155,84 @@ def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4
         # a query none of whose proposal sequences carries a colour has no prediction (idx -1): never index rects[-1]
         out[gi] = (idx, rects[idx] if 0 <= idx < len(rects) else None)
     return out
+
+
+def _gather_ranges(buf, bounds):
+    """buf (n_total, ...) holds this rank's range [bounds[rank], bounds[rank + 1]) of a ragged split; every rank gets the whole tensor: one
+    fixed-shape all_gather, padded to the longest range."""
+    rank, world = cdist.rank_world()
+    if world == 1:
+        return buf
+    mx = max(max(bounds[r + 1] - bounds[r] for r in range(world)), 1)
+    pad = torch.zeros((mx,) + tuple(buf.shape[1:]), dtype=buf.dtype, device=buf.device)
+    pad[:bounds[rank + 1] - bounds[rank]] = buf[bounds[rank]:bounds[rank + 1]]
+    bufs = [torch.empty_like(pad) for _ in range(world)]
+    torch.distributed.all_gather(bufs, pad)
+    return torch.cat([bufs[r][:bounds[r + 1] - bounds[r]] for r in range(world)], 0)
+
+
+def val_rec(model, queries, gts, none_id, device, few_shot=False, batch_queries=4, colour_columns_only=True, trim=False, bucket=False,
+            max_sequences=None, table=None, return_candidate_scores=False):
+    """The whole of val() (zeroshot/refcoco_cpt.py:208-288, fewshot/refcoco_cpt.py:258-315) with the evaluation on the device: the pass of
+    val_queries -- same queries, sharding, walking and trim / bucket / max_sequences -- whose step is concatenate, one forward, ONE launch
+    (cpt_rec_choose): selection, the chosen box's float64 IoU against the annotation, correct = IoU > 0.5 and the counts, against tables
+    uploaded once (scoring.rec_eval_table; pass ``table`` to reuse one over several passes of a split).  Per step only the batch's query
+    indices are uploaded and nothing is read back.  gts: per query its annotation [x, y, w, h] or None.
+    Returns {"accuracy": percent = correct / evaluated, the number val() returns, "n_evaluated", "n_unpredicted" (queries without a colour),
+    "predictions": {query index: (idx, rect)} as val_queries returns, "correct" (Q,) uint8, "iou" (Q,) float64, "score" (Q,) fp32 host arrays,
+    and with return_candidate_scores "candidate_scores" (R_total,) fp32: every candidate's score, val()'s to_save_predictions[k]["scores"]
+    concatenated} on every rank.  A query without a colour or without an annotation is counted in neither sum."""
+    model.eval()
+    if table is None:
+        col_ids = sorted({int(c) for q in queries for s in q["colors"] for c in s} | {int(none_id)}) if colour_columns_only else None
+        table = scoring.rec_eval_table(queries, gts, none_id, col_ids)
+    if table["n_queries"] != len(queries) or (table["col_ids"] is None) == bool(colour_columns_only) or table["none_id"] != int(none_id):
+        raise ValueError("val_rec: the table was built for other queries, another none_id or another colour_columns_only")
+    cols_dev = None if table["col_ids"] is None else torch.tensor(table["col_ids"], dtype=torch.int64, device=device)
+    scoring.rec_table_device(table, device)
+    out = scoring.rec_eval_buffers(table, device, return_candidate_scores)
+
+    def groups_of(lo, hi):
+        shard = queries[lo:hi]
+        keys = [_item_length(q["attention_mask"], q["input_ids"].shape[1]) for q in shard] if bucket else None
+        counts = [q["input_ids"].size(0) for q in shard] if max_sequences is not None else None
+        return _walk(hi - lo, batch_queries, keys, counts, max_sequences)
+
+    def step(idx_local, lo):
+        cat = {k: torch.cat([queries[lo + i][k] for i in idx_local], 0)
+               for k in ("img_feats", "input_ids", "segment_ids", "attention_mask", "mask_token_pos")}
+        if trim:
+            cat = _trim_host(cat, cat["mask_token_pos"])[0]
+        cat = {k: v.to(device, non_blocking=True) for k, v in cat.items()}
+        scores = model(cat["input_ids"], cat["segment_ids"], cat["attention_mask"], img_feats=cat["img_feats"],
+                       mask_token_pos=cat["mask_token_pos"], vocab_columns=cols_dev)[0]
+        scoring.rec_choose_device(scores, [lo + i for i in idx_local], table, few_shot, out)
+        return ()
+
+    n = len(queries)
+    _eval_pass(n, groups_of, [], step, device, bucket)
+    rank, world = cdist.rank_world()
+    lo, hi = cdist.shard_range(n, rank, world)
+    idx, score, iou, correct = (cdist.gather_fixed(out[k][lo:hi], n) for k in ("idx", "score", "iou", "correct"))
+    counts = out["counts"]
+    if world > 1:       # (the counts of every rank's shard, summed)
+        every = [torch.empty_like(counts) for _ in range(world)]
+        torch.distributed.all_gather(every, counts)
+        counts = torch.stack(every).sum(0)
+    n_correct, n_eval = counts.cpu().tolist()
+    chosen = idx.cpu().tolist()
+    res = {"accuracy": n_correct / max(n_eval, 1) * 100, "n_evaluated": n_eval, "n_unpredicted": sum(1 for i in chosen if i < 0),
+           "correct": correct.cpu().numpy(), "iou": iou.cpu().numpy(), "score": score.cpu().numpy()}
+    if return_candidate_scores:
+        cf = table["cand_first"].tolist()
+        bounds = [cf[cdist.shard_range(n, r, world)[0]] for r in range(world)] + [cf[n]]
+        res["candidate_scores"] = _gather_ranges(out["cand_score"], bounds).cpu().numpy()
+    preds = {}
+    for gi, i in enumerate(chosen):
+        rects = [r for rs in queries[gi]["rects"] for r in rs]
+        preds[gi] = (i, rects[i] if 0 <= i < len(rects) else None)
+    res["predictions"] = preds
+    return res
 
 
 def _label_grid(batch):

@@ -2,8 +2,11 @@
 
 Counterparts of /root/reference/Oscar/oscar/zeroshot/refcoco_cpt.py:219-254 (raw colour logits),
 Oscar/oscar/fewshot/refcoco_cpt.py:277-295 (colour logit / "none" logit) and
-Oscar/oscar/utils/iou.py:1-12.  Host-side: the inputs are the (B, V) [MASK]-row logits the HIP path
-returns; only B x n_colour values are touched, and torch.argmax's first-max tie-break is kept.
+Oscar/oscar/utils/iou.py:1-12.  Two forms.  Host-side (select_region, compute_iou, accuracy): the inputs
+are the (B, V) [MASK]-row logits the HIP path returns; only B x n_colour values are touched, and
+torch.argmax's first-max tie-break is kept.  On the device (rec_eval_table + rec_choose_device, what
+drivers.val_rec runs): the selection, the float64 IoU and the accuracy counts of a batch in one launch
+(cpt_rec_choose) against tables uploaded once per split; rec_eval_reference is its host yardstick.
 """
 import numpy as np
 import torch
@@ -89,6 +92,190 @@ def select_regions_device(mask_scores, color_id_sets, query_first, none_id, few_
     L.check(L.lib().cpt_select_regions(ms.data_ptr(), V, ids.data_ptr(), C, qf.data_ptr(), Q, int(none_id), 1 if few_shot else 0,
                                        out.data_ptr(), L.ptr(sc), L.stream_ptr()), "cpt_select_regions")
     return (out, sc) if return_scores else out
+
+
+# ---- RefCOCO REC evaluation on the device (zeroshot/refcoco_cpt.py:224-246, 267-280; fewshot/refcoco_cpt.py:277-297, 305-315) ----------------
+def rec_eval_table(queries, gts, none_id, col_ids=None, device=None):
+    """val()'s bookkeeping as flat tables, once per split.  queries: the dicts drivers.val_queries takes (``colors``: per proposal sequence its
+    colour-token ids, ``rects``: per sequence its x1, y1, x2, y2 rectangles); gts: per query its annotation [x, y, w, h] or None (a list, or a dict
+    keyed by query index); col_ids: the vocabulary column list the scores are computed for (drivers' colour_columns_only) -- colour ids and
+    none_id then become positions in it.  Raises ValueError, before anything runs, for a rectangle that breaks the reference's
+    ``x2 > x1 and y2 > y1`` assert (any candidate may be the chosen one), for a sequence whose colour count differs from its rectangle count,
+    and for a non-finite annotation.
+    Returns a dict of CPU tensors -- seq_first (Q + 1,) int32, cols (S_total, C) int32 (-1 = trailing padding), cand_first (Q + 1,) int32,
+    rects (R_total, 4) float64 in val()'s concatenation order, gt (Q, 4) float64, has_gt (Q,) uint8 -- plus n_queries, C, none (the "none"
+    column), none_id, col_ids and n_cols_min (the columns the scores need at least).  device: upload now (rec_table_device); otherwise on first
+    use."""
+    col_of = None if col_ids is None else {int(c): i for i, c in enumerate(col_ids)}
+
+    def column(c, what):
+        if col_of is None:
+            return int(c)
+        if int(c) not in col_of:
+            raise ValueError("cpt_amd: %s id %d is not in the column list" % (what, int(c)))
+        return col_of[int(c)]
+
+    none = column(none_id, '"none"')
+    seq_first, cand_first, col_rows, rects = [0], [0], [], []
+    for qi, q in enumerate(queries):
+        if len(q["colors"]) != len(q["rects"]):
+            raise ValueError("cpt_amd: query %d has %d colour sets and %d rectangle sets" % (qi, len(q["colors"]), len(q["rects"])))
+        for si, (cs, rs) in enumerate(zip(q["colors"], q["rects"])):
+            if len(cs) != len(rs):
+                raise ValueError("cpt_amd: query %d sequence %d has %d colours and %d rectangles" % (qi, si, len(cs), len(rs)))
+            for r in rs:
+                if len(r) != 4 or not (r[2] > r[0] and r[3] > r[1]):
+                    raise ValueError("cpt_amd: query %d sequence %d holds the degenerate rectangle %s (val() asserts x2 > x1 and y2 > y1)"
+                                     % (qi, si, list(r)))
+                rects.append([float(x) for x in r])
+            col_rows.append([column(c, "colour") for c in cs])
+        seq_first.append(len(col_rows))
+        cand_first.append(len(rects))
+    Q = len(queries)
+    C = max(1, max((len(r) for r in col_rows), default=1))
+    cols = torch.full((max(len(col_rows), 1), C), -1, dtype=torch.int32)[:len(col_rows)]
+    for i, r in enumerate(col_rows):
+        if r:
+            cols[i, :len(r)] = torch.tensor(r, dtype=torch.int32)
+    gt = torch.zeros((Q, 4), dtype=torch.float64)
+    has_gt = torch.zeros(Q, dtype=torch.uint8)
+    for qi in range(Q):
+        g = gts.get(qi) if isinstance(gts, dict) else gts[qi]
+        if g is None:
+            continue
+        g = [float(x) for x in g]
+        if len(g) != 4 or not all(np.isfinite(g)):
+            raise ValueError("cpt_amd: query %d has the annotation %s (four finite numbers x, y, w, h)" % (qi, g))
+        gt[qi] = torch.tensor(g, dtype=torch.float64)
+        has_gt[qi] = 1
+    i32 = torch.int32
+    table = {"seq_first": torch.tensor(seq_first, dtype=i32), "cols": cols.contiguous(), "cand_first": torch.tensor(cand_first, dtype=i32),
+             "rects": torch.tensor(rects, dtype=torch.float64).view(-1, 4), "gt": gt, "has_gt": has_gt, "n_queries": Q, "C": C, "none": none,
+             "none_id": int(none_id), "col_ids": None if col_ids is None else [int(c) for c in col_ids],
+             "n_cols_min": max(none, int(cols.max()) if cols.numel() else 0) + 1, "_seq_first": seq_first}
+    if device is not None:
+        rec_table_device(table, device)
+    return table
+
+
+_REC_TABLE_KEYS = ("seq_first", "cols", "cand_first", "rects", "gt", "has_gt")
+
+
+def rec_table_device(table, device):
+    """The six tables of rec_eval_table on ``device``: packed into one byte buffer on the host (16-byte aligned pieces), ONE upload, typed
+    views of it.  Cached in the table per device."""
+    device = torch.device(device)
+    dt = table.get("_dev")
+    if dt is not None and dt[0] == device:
+        return dt[1]
+    offs, total = {}, 0
+    for k in _REC_TABLE_KEYS:
+        offs[k] = total
+        total += (table[k].numel() * table[k].element_size() + 15) // 16 * 16
+    host = torch.zeros(max(total, 16), dtype=torch.uint8)
+    for k in _REC_TABLE_KEYS:
+        b = table[k].contiguous().view(-1).view(torch.uint8)
+        host[offs[k]:offs[k] + b.numel()] = b
+    buf = host.to(device)
+    views = {}
+    for k in _REC_TABLE_KEYS:
+        n = table[k].numel() * table[k].element_size()
+        views[k] = buf[offs[k]:offs[k] + n].view(table[k].dtype).view(table[k].shape)
+    views["_buffer"] = buf
+    table["_dev"] = (device, views)
+    return views
+
+
+def rec_eval_buffers(table, device, candidate_scores=False):
+    """The result buffers of one evaluation pass on the device, one slot per query of the split: idx int32 (-1), score fp32 (0), iou float64
+    (NaN), correct uint8 (0), counts (2,) int32 = (correct, evaluated), zeroed, and cand_score (R_total,) fp32 (0) or None."""
+    Q = table["n_queries"]
+    return {"idx": torch.full((Q,), -1, dtype=torch.int32, device=device), "score": torch.zeros(Q, dtype=torch.float32, device=device),
+            "iou": torch.full((Q,), float("nan"), dtype=torch.float64, device=device), "correct": torch.zeros(Q, dtype=torch.uint8, device=device),
+            "counts": torch.zeros(2, dtype=torch.int32, device=device),
+            "cand_score": torch.zeros(table["rects"].size(0), dtype=torch.float32, device=device) if candidate_scores else None}
+
+
+def rec_choose_device(mask_scores, q_index, table, few_shot, out):
+    """cpt_rec_choose, one launch: mask_scores (S_b, V') fp32 on the GPU, the head rows of the queries ``q_index`` (global indices in table
+    order, any order, each once) one after the other; ``out`` the buffers of rec_eval_buffers, written at the queries' global indices and
+    counted into out["counts"].  Only q_index is uploaded, nothing is read back.  The sizes are checked on the host against the table."""
+    from . import _lib as L
+    if not mask_scores.is_cuda:
+        raise RuntimeError("cpt_amd: rec_choose_device needs the logits on the GPU (no CPU fallback: rec_eval_reference is the host form)")
+    dev = mask_scores.device
+    qi = [int(i) for i in q_index]
+    Q = table["n_queries"]
+    S, V = mask_scores.shape
+    if not qi or min(qi) < 0 or max(qi) >= Q or len(set(qi)) != len(qi):
+        raise ValueError("cpt_amd: rec_choose_device takes distinct query indices in [0, %d)" % Q)
+    sf = table["_seq_first"]
+    n_seq = sum(sf[i + 1] - sf[i] for i in qi)
+    if n_seq != S or V < table["n_cols_min"] or mask_scores.dtype != torch.float32:
+        raise ValueError("cpt_amd: rec_choose_device got %s %s scores; the %d queries hold %d sequences and read column %d"
+                         % (tuple(mask_scores.shape), mask_scores.dtype, len(qi), n_seq, table["n_cols_min"] - 1))
+    for k, dtype, n in (("idx", torch.int32, Q), ("score", torch.float32, Q), ("iou", torch.float64, Q), ("correct", torch.uint8, Q),
+                        ("counts", torch.int32, 2), ("cand_score", torch.float32, table["rects"].size(0))):
+        t = out[k]
+        if t is None and k == "cand_score":
+            continue
+        if t.dtype != dtype or t.numel() != n or t.device != dev or not t.is_contiguous():
+            raise ValueError("cpt_amd: rec_choose_device out[%r] must be a contiguous %s tensor of %d elements on %s" % (k, dtype, n, dev))
+    t = rec_table_device(table, dev)
+    qd = torch.tensor(qi, dtype=torch.int32).to(dev, non_blocking=True)
+    ms = mask_scores.contiguous()
+    L.check(L.lib().cpt_rec_choose(ms.data_ptr(), S, V, qd.data_ptr(), len(qi), Q, t["seq_first"].data_ptr(), t["cols"].data_ptr(), table["C"],
+                                   t["cand_first"].data_ptr(), t["rects"].data_ptr(), t["gt"].data_ptr(), t["has_gt"].data_ptr(), table["none"],
+                                   1 if few_shot else 0, out["idx"].data_ptr(), out["score"].data_ptr(), out["iou"].data_ptr(),
+                                   out["correct"].data_ptr(), L.ptr(out["cand_score"]), out["counts"].data_ptr(), L.stream_ptr()), "cpt_rec_choose")
+    return out
+
+
+def rec_eval_reference(mask_scores, table, few_shot=False):
+    """The host yardstick of cpt_rec_choose, no device call: the two val() post-loops (zeroshot/refcoco_cpt.py:224-246, 267-280;
+    fewshot/refcoco_cpt.py:277-297, 305-315) and compute_iou restated literally in torch and Python floats.  mask_scores (S_total, V') CPU fp32:
+    the head row of every sequence of the table, in order.  A query without a colour (the reference's torch.cat would raise) gets idx -1,
+    score -inf; it and a query without an annotation (the reference's gts[k] would raise) get iou NaN and count in neither sum.
+    Returns {"idx" (Q,) int32, "score" (Q,) fp32, "iou" (Q,) float64, "correct" (Q,) uint8, "cand_score" (R_total,) fp32 numpy arrays,
+    "rects": per query the chosen x1, y1, x2, y2 or None, "counts": [correct, evaluated], "accuracy": percent}."""
+    sf, cf = table["seq_first"].tolist(), table["cand_first"].tolist()
+    cols, none = table["cols"].tolist(), table["none"]
+    all_rects, gts, has_gt = table["rects"].tolist(), table["gt"].tolist(), table["has_gt"].tolist()
+    Q = table["n_queries"]
+    idx = np.full(Q, -1, dtype=np.int32)
+    score = np.full(Q, -np.inf, dtype=np.float32)
+    iou_out = np.full(Q, float("nan"), dtype=np.float64)
+    flags = np.zeros(Q, dtype=np.uint8)
+    cand_score = np.zeros(len(all_rects), dtype=np.float32)
+    predictions = {}
+    for q in range(Q):
+        collected_rects = all_rects[cf[q]:cf[q + 1]]
+        collected_scores = []
+        for s in range(sf[q], sf[q + 1]):
+            cur_color_id_set = [c for c in cols[s] if c >= 0] + [none]
+            cur_color_scores = mask_scores[s][cur_color_id_set]
+            collected_scores.append(cur_color_scores[0:-1] / cur_color_scores[-1] if few_shot else cur_color_scores[0:-1])
+        if not collected_rects:
+            continue
+        collected_scores = torch.cat(collected_scores, -1)
+        max_idx = collected_scores.argmax()
+        predictions[q] = collected_rects[int(max_idx)]
+        idx[q] = int(max_idx)
+        score[q] = collected_scores[int(max_idx)].numpy()
+        cand_score[cf[q]:cf[q + 1]] = collected_scores.numpy()
+    miou, n = 0, 0
+    for k, p in predictions.items():
+        if not has_gt[k]:
+            continue
+        assert p[2] > p[0] and p[3] > p[1]
+        p = [p[0], p[1], p[2] - p[0] + 1, p[3] - p[1] + 1]
+        iou = compute_iou(p, gts[k])
+        miou += iou > 0.5
+        n += 1
+        iou_out[k] = iou
+        flags[k] = iou > 0.5
+    return {"idx": idx, "score": score, "iou": iou_out, "correct": flags, "cand_score": cand_score,
+            "rects": [predictions.get(q) for q in range(Q)], "counts": [int(miou), n], "accuracy": miou / max(n, 1) * 100}
 
 
 def argmax_columns_device(scores, ids):

@@ -546,6 +546,23 @@ int cpt_select_regions(const float* mask_logits, int V, const int64_t* color_ids
 int cpt_argmax_columns(const float* logits, int V, const int64_t* ids, int n_ids, int R, int64_t* out_idx, float* out_val,
                        void* stream);
 
+/* RefCOCO REC evaluation of one batch of queries, one launch: the selection of cpt_select_regions, then the two val() post-loops and computeIoU
+ * (Oscar/oscar/zeroshot/refcoco_cpt.py:224-246, 267-280; fewshot/refcoco_cpt.py:277-297, 305-315; utils/iou.py:1-13).  Added beside ABI 8, no
+ * struct changed.  The split's tables live on the device (built once: cpt_amd/scoring.py rec_eval_table), for Q queries in data set order:
+ *   seq_first [Q + 1] int32   first proposal sequence of every query       cols [S_total][C] int32   colour columns of every sequence, -1 = trailing padding
+ *   cand_first [Q + 1] int32  first candidate of every query               rects [R_total][4] double  x1, y1, x2, y2 (x2 > x1, y2 > y1: the builder checks)
+ *   gt [Q][4] double          the annotation x, y, w, h                    has_gt [Q] uint8
+ * scores [S][V] fp32 are the batch's head rows: the sequences of query q_index[0], then of q_index[1], ... (q_index [Qb] int32, global query
+ * indices in any order, each once).  A candidate's score is scores[row][col], divided by scores[row][none] when divide_by_none (the fp32 division).
+ * Per query, at its GLOBAL index: idx int32 = the argmax inside the query's concatenation (torch.argmax: first maximum, NaN maximal, -0 == +0;
+ * -1 for a query without a colour), score fp32 its value, iou double = computeIoU([x1, y1, x2 - x1 + 1, y2 - y1 + 1], gt) in float64 in Python's
+ * operation order without contraction (NaN for a query without a colour or without an annotation), correct uint8 = iou > 0.5.  cand_score
+ * [R_total] fp32 (may be NULL) takes every candidate's score.  counts [2] int32 += (correct, evaluated) by integer atomics: zero it once per pass;
+ * a query without a colour or without an annotation counts in neither. */
+int cpt_rec_choose(const float* scores, int S, int V, const int32_t* q_index, int Qb, int Q, const int32_t* seq_first, const int32_t* cols, int C,
+                   const int32_t* cand_first, const double* rects, const double* gt, const uint8_t* has_gt, int none, int divide_by_none,
+                   int32_t* idx, float* score, double* iou, uint8_t* correct, float* cand_score, int32_t* counts, void* stream);
+
 /* Fold LayerNorm(gamma, beta) into the Linear (W [N][K] fp32, bias [N] or NULL) that consumes its output:
  * Wf = bf16(gamma[k] * W[n][k]), colc[n] = sum_k Wf[n][k], cold[n] = sum_k beta[k] W[n][k] + bias[n]. */
 int cpt_fold_ln_weights(const float* W, const float* gamma, const float* beta, const float* bias, void* Wf_bf16,
