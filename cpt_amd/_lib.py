@@ -160,6 +160,10 @@ _SIGS = {
     "cpt_gemm_ln_prod3_rpanel": (C.c_int, [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "cpt_gemm_tile": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "cpt_gemm_ln_cons_tile": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    "cpt_gemm_ln_prod_tile": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int, vp, vp, vp, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, vp]),
+    "cpt_gemm_ln_prod3_tile": (C.c_int, [C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int, vp, vp, vp, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, vp]),
     "cpt_gemm_ln_prod3_panel_waves": (C.c_int, [C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_float, C.c_int, vp, vp, vp, C.c_int, C.c_int,
                                                 C.c_int, C.c_int, vp]),
     "cpt_resid3_split": (C.c_int, [vp, vp, vp, C.c_size_t, vp]),

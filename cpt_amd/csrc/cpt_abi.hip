@@ -415,6 +415,18 @@ int cpt_gemm_ln_cons_tile(int tile, const void* A_bf16, int lda, const void* Wf_
     cpt::OverrideScope sc(tile, -1);
     return cpt_gemm_ln_cons(A_bf16, lda, Wf_bf16, ldw, st_in, colc, cold, eps, hidden, gelu, out_bf16, ldo, M, N, K, stream);
 }
+int cpt_gemm_ln_prod_tile(int tile, const void* A, int lda, const void* W, int ldw, const float* bias, const float* resid, int ldr, const float* st_in,
+                          const float* g_in, const float* b_in, float eps, int hidden, float* out_f32, void* out_lp, float* st_out, int ldo,
+                          int M, int N, int K, void* stream) {
+    cpt::OverrideScope sc(tile, -1);
+    return cpt_gemm_ln_prod(A, lda, W, ldw, bias, resid, ldr, st_in, g_in, b_in, eps, hidden, out_f32, out_lp, st_out, ldo, M, N, K, stream);
+}
+int cpt_gemm_ln_prod3_tile(int tile, const void* A, int lda, const void* W, int ldw, const float* bias, const void* resid_hi, const void* resid_lo, int ldr,
+                           const float* st_in, const float* g_in, const float* b_in, float eps, int hidden, void* out_hi, void* out_lo,
+                           float* st_out, int ldo, int M, int N, int K, void* stream) {
+    cpt::OverrideScope sc(tile, -1);
+    return cpt_gemm_ln_prod3(A, lda, W, ldw, bias, resid_hi, resid_lo, ldr, st_in, g_in, b_in, eps, hidden, out_hi, out_lo, st_out, ldo, M, N, K, stream);
+}
 int cpt_gemm_ln_prod3_panel_waves(int waves, const void* A_panel, const void* W, int ldw, const float* bias, const void* resid_hi, const void* resid_lo, int ldr,
                                   const float* st_in, const float* g_in, const float* b_in, float eps, int hidden, void* out_hi, void* out_lo,
                                   float* st_out, int ldo, int M, int N, int K, void* stream) {

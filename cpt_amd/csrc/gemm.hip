@@ -1754,6 +1754,14 @@ int gemm_nn(const void* A, int lda, const void* W, int ldw, const float* resid, 
 int ln_stat_parts(int n_cols) { return (n_cols + 95) / 96; }     // 96-column blocks of an n_cols-wide producer
 int ln_stat_slots(int n_cols) { return (ln_stat_parts(n_cols) + 1) & ~1; }   // slots per row of its table [M][slots][2]
 
+// The producers' tile for this call.  A FORCED 128 x 384 tile (variant 10; the by-shape model never takes it there) whose last column tile reaches past
+// the table's slots -- N mod 384 in (0, 192]: slots = 2 ceil(N / 192) < 4 ceil(N / 384) -- would store the row sums of its columns beyond N, zeros, into
+// the NEXT row's first slots and, for the last row, behind the table: such a call runs the 128 x 192 tile, whose column tiles end with the slots.
+static int ln_prod_variant(int N) {
+    const int v = g_gemm_variant >= 3 ? g_gemm_variant : 3;
+    return (v == 10 && 4 * ((N + 383) / 384) > ln_stat_slots(N)) ? 13 : v;
+}
+
 int gemm_ln_prod(const void* A, int lda, const void* W, int ldw, const float* bias, const float* resid, int ldr,
                  const float* st_in, const float* g_in, const float* b_in, float eps, int hidden,
                  float* out_f32, void* out_lp, float* st_out, int ldo, int M, int N, int K, hipStream_t s) {
@@ -1765,7 +1773,7 @@ int gemm_ln_prod(const void* A, int lda, const void* W, int ldw, const float* bi
     EpiX ex = {};
     ex.st_in = st_in; ex.st_in_parts = ln_stat_parts(hidden); ex.g_in = g_in; ex.b_in = b_in; ex.st_out = st_out; ex.st_out_slots = ln_stat_slots(N); ex.out_lp = out_lp;
     ex.eps = eps; ex.inv_h = 1.0f / (float)hidden;
-    launch_fast<bf16, CPT_EPI_LNPROD, float>(g_gemm_variant >= 3 ? g_gemm_variant : 3, (const bf16*)A, lda, (const bf16*)W, ldw, bias,
+    launch_fast<bf16, CPT_EPI_LNPROD, float>(ln_prod_variant(N), (const bf16*)A, lda, (const bf16*)W, ldw, bias,
                                             resid, ldr, out_f32, ldo, M, N, K, s, &ex);
     return CPT_OK;
 }
@@ -1783,7 +1791,7 @@ int gemm_ln_prod3(const void* A, int lda, const void* W, int ldw, const float* b
     ex.st_in = st_in; ex.st_in_parts = ln_stat_parts(hidden); ex.g_in = g_in; ex.b_in = b_in; ex.st_out = st_out; ex.st_out_slots = ln_stat_slots(N); ex.out_lp = out_hi;
     ex.resid_lo = (const signed char*)resid_lo; ex.out_lo = (signed char*)out_lo;
     ex.eps = eps; ex.inv_h = 1.0f / (float)hidden;
-    launch_fast<bf16, CPT_EPI_LNPROD3, float>(g_gemm_variant >= 3 ? g_gemm_variant : 3, (const bf16*)A, lda, (const bf16*)W, ldw, bias,
+    launch_fast<bf16, CPT_EPI_LNPROD3, float>(ln_prod_variant(N), (const bf16*)A, lda, (const bf16*)W, ldw, bias,
                                              (const float*)resid_hi, ldr, (float*)nullptr, ldo, M, N, K, s, &ex);
     return CPT_OK;
 }

@@ -180,18 +180,30 @@ def resid3_merge(hi, lo, pos=None, L_rows=None):
     return out
 
 
-def gemm_ln_prod3(a, w, bias, resid_hi, resid_lo, st_in=None, g_in=None, b_in=None, eps=1e-12, hidden=None):
-    """gemm_ln_prod with the residual and the output in the 3-byte form: returns (out_hi bf16, out_lo int8, st_out)."""
-    _need_cuda(a, w, bias, resid_hi, resid_lo)
+def gemm_ln_prod3(a, w, bias, resid_hi, resid_lo, st_in=None, g_in=None, b_in=None, eps=1e-12, hidden=None, tile=None, out_hi=None, out_lo=None,
+                  st_out=None):
+    """gemm_ln_prod with the residual and the output in the 3-byte form: returns (out_hi bf16, out_lo int8, st_out).  tile: one of the shipped tile
+    configurations for THIS call (cpt_gemm_ln_prod3_tile; None: by shape); out_hi / out_lo / st_out: the caller's buffers (row stride = out_hi's)."""
+    _need_cuda(a, w, bias, resid_hi, resid_lo, out_hi, out_lo, st_out)
     M, K = a.shape
     N = w.size(0)
     hidden = hidden or N
-    out_hi = torch.empty((M, N), device=a.device, dtype=torch.bfloat16)
-    out_lo = torch.empty((M, N), device=a.device, dtype=torch.int8)
-    st_out = torch.zeros((M, ln_stat_slots(N), 2), device=a.device, dtype=torch.float32)
-    L.check(L.lib().cpt_gemm_ln_prod3(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), L.ptr(bias), resid_hi.data_ptr(), resid_lo.data_ptr(),
-                                      resid_hi.stride(0), L.ptr(st_in), L.ptr(g_in), L.ptr(b_in), float(eps), hidden, out_hi.data_ptr(),
-                                      out_lo.data_ptr(), st_out.data_ptr(), out_hi.stride(0), M, N, K, L.stream_ptr()), "cpt_gemm_ln_prod3")
+    if out_hi is None:
+        out_hi = torch.empty((M, N), device=a.device, dtype=torch.bfloat16)
+    if out_lo is None:
+        out_lo = torch.empty((M, N), device=a.device, dtype=torch.int8)
+    if st_out is None:
+        st_out = torch.zeros((M, ln_stat_slots(N), 2), device=a.device, dtype=torch.float32)
+    assert out_hi.dtype == torch.bfloat16 and out_lo.dtype == torch.int8 and out_hi.shape == (M, N) and out_lo.shape == (M, N)
+    assert out_hi.stride(1) == 1 and out_lo.stride(1) == 1 and out_lo.stride(0) == out_hi.stride(0)
+    assert st_out.dtype == torch.float32 and st_out.shape == (M, ln_stat_slots(N), 2) and st_out.is_contiguous()
+    args = (a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), L.ptr(bias), resid_hi.data_ptr(), resid_lo.data_ptr(),
+            resid_hi.stride(0), L.ptr(st_in), L.ptr(g_in), L.ptr(b_in), float(eps), hidden, out_hi.data_ptr(),
+            out_lo.data_ptr(), st_out.data_ptr(), out_hi.stride(0), M, N, K, L.stream_ptr())
+    if tile is None:
+        L.check(L.lib().cpt_gemm_ln_prod3(*args), "cpt_gemm_ln_prod3")
+    else:
+        L.check(L.lib().cpt_gemm_ln_prod3_tile(int(tile), *args), "cpt_gemm_ln_prod3_tile")
     return out_hi, out_lo, st_out
 
 
@@ -275,17 +287,28 @@ def gemm_ln_cons(a, wf, st_in, colc, cold, eps, hidden, gelu, tile=None):
     return out
 
 
-def gemm_ln_prod(a, w, bias, resid, st_in=None, g_in=None, b_in=None, eps=1e-12, hidden=None):
+def gemm_ln_prod(a, w, bias, resid, st_in=None, g_in=None, b_in=None, eps=1e-12, hidden=None, tile=None, out=None, out_lp=None, st_out=None):
     """out = a @ w.T + bias + R with R = resid, or LayerNorm(resid; st_in, g_in, b_in) when g_in is given.
-    Returns (out_f32, out_bf16, st_out) -- st_out = partial row sums of out (the table the next consumer reads)."""
-    _need_cuda(a, w, bias, resid)
+    Returns (out_f32, out_bf16, st_out) -- st_out = partial row sums of out (the table the next consumer reads).  tile: one of the shipped
+    tile configurations for THIS call (cpt_gemm_ln_prod_tile; None: by shape); out / out_lp / st_out: the caller's buffers (row stride = out's)."""
+    _need_cuda(a, w, bias, resid, out, out_lp, st_out)
     M, K = a.shape
     N = w.size(0)
     hidden = hidden or N
-    out = torch.empty((M, N), device=a.device, dtype=torch.float32)
-    out_lp = torch.empty((M, N), device=a.device, dtype=torch.bfloat16)
-    st_out = torch.zeros((M, ln_stat_slots(N), 2), device=a.device, dtype=torch.float32)
-    L.check(L.lib().cpt_gemm_ln_prod(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), L.ptr(bias), resid.data_ptr(), resid.stride(0),
-                                     L.ptr(st_in), L.ptr(g_in), L.ptr(b_in), float(eps), hidden, out.data_ptr(), out_lp.data_ptr(),
-                                     st_out.data_ptr(), out.stride(0), M, N, K, L.stream_ptr()), "cpt_gemm_ln_prod")
+    if out is None:
+        out = torch.empty((M, N), device=a.device, dtype=torch.float32)
+    if out_lp is None:
+        out_lp = torch.empty((M, N), device=a.device, dtype=torch.bfloat16)
+    if st_out is None:
+        st_out = torch.zeros((M, ln_stat_slots(N), 2), device=a.device, dtype=torch.float32)
+    assert out.dtype == torch.float32 and out_lp.dtype == torch.bfloat16 and out.shape == (M, N) and out_lp.shape == (M, N)
+    assert out.stride(1) == 1 and out_lp.stride(1) == 1 and out_lp.stride(0) == out.stride(0)
+    assert st_out.dtype == torch.float32 and st_out.shape == (M, ln_stat_slots(N), 2) and st_out.is_contiguous()
+    args = (a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), L.ptr(bias), resid.data_ptr(), resid.stride(0),
+            L.ptr(st_in), L.ptr(g_in), L.ptr(b_in), float(eps), hidden, out.data_ptr(), out_lp.data_ptr(),
+            st_out.data_ptr(), out.stride(0), M, N, K, L.stream_ptr())
+    if tile is None:
+        L.check(L.lib().cpt_gemm_ln_prod(*args), "cpt_gemm_ln_prod")
+    else:
+        L.check(L.lib().cpt_gemm_ln_prod_tile(int(tile), *args), "cpt_gemm_ln_prod_tile")
     return out, out_lp, st_out

@@ -29,11 +29,21 @@ int cpt_prof_read(int kernel_id, double* total_ms, int64_t* launches); /* synchr
  * small problems with these.  The choice is an argument of the call (thread-local for its duration): no state survives it.
  *   tile (cpt_gemm_tile, cpt_gemm_ln_cons_tile): 3 = by shape; 0 = generic register-staged kernel; 13 = 128x192 (3-stage), 11 = 192x192, 10 = 128x384,
  *     14 = 384x192, 15 = 128x192 two workgroups per CU, 18 = 64x192, 19 = 384x256 one pass; consumers also 20 = two-pass 384x256, 21 = 4-wave 192x256
+ *   tile (cpt_gemm_ln_prod_tile, cpt_gemm_ln_prod3_tile): 3 = by shape; 13 = 128x192, 18 = 64x192, 11 = 192x192, 10 = 128x384; cpt_gemm_ln_prod3_tile also
+ *     15 = 128x192 two workgroups per CU.  The LayerNorm-producer epilogue has no other instantiation: any other id above 3 (14, 19, ...; 15 for
+ *     cpt_gemm_ln_prod_tile) runs the 128x192 kernel, and so does 10 at a width whose last 384-column tile would reach past the row-sum table's
+ *     slots (N mod 384 in 1..192); an id below 3 chooses by shape
  *   waves (cpt_gemm_ln_prod3_panel_waves; also an argument of cpt_gemm_ln_prod3_rpanel in cpt_hip.h): 0 = by shape, 8 = 4x2 waves of 32x96, 4 = 4x1 waves of 32x192 */
 int cpt_gemm_tile(int tile, int dtype, int epi, const void* A, int lda, const void* W, int ldw, const float* bias,
                   const float* resid, int ldr, void* out, int out_dtype, int ldo, int M, int N, int K, void* stream);
 int cpt_gemm_ln_cons_tile(int tile, const void* A_bf16, int lda, const void* Wf_bf16, int ldw, const float* st_in, const float* colc,
                           const float* cold, float eps, int hidden, int gelu, void* out_bf16, int ldo, int M, int N, int K, void* stream);
+int cpt_gemm_ln_prod_tile(int tile, const void* A_bf16, int lda, const void* W_bf16, int ldw, const float* bias, const float* resid, int ldr,
+                          const float* st_in, const float* g_in, const float* b_in, float eps, int hidden, float* out_f32, void* out_bf16,
+                          float* st_out, int ldo, int M, int N, int K, void* stream);
+int cpt_gemm_ln_prod3_tile(int tile, const void* A_bf16, int lda, const void* W_bf16, int ldw, const float* bias, const void* resid_hi, const void* resid_lo,
+                           int ldr, const float* st_in, const float* g_in, const float* b_in, float eps, int hidden, void* out_hi, void* out_lo,
+                           float* st_out, int ldo, int M, int N, int K, void* stream);
 int cpt_gemm_ln_prod3_panel_waves(int waves, const void* A_panel, const void* W_bf16, int ldw, const float* bias, const void* resid_hi, const void* resid_lo,
                                   int ldr, const float* st_in, const float* g_in, const float* b_in, float eps, int hidden, void* out_hi, void* out_lo,
                                   float* st_out, int ldo, int M, int N, int K, void* stream);

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from _lnref import _r3_decode_np, _r3_encode_np      # the 3-byte code's restatement lives beside the float64 LayerNorm-GEMM reference
+
 pytestmark = pytest.mark.gpu
 
 
@@ -393,20 +395,6 @@ def test_gemm_nn_split_k_and_row_bound(dev):
         assert torch.isfinite(got).all()
         assert (got - ref).abs().max().item() < 2e-3, (scratch, (got - ref).abs().max().item())
     assert torch.equal(ops.gemm_nn(a, w, None, torch.float32, split_scratch=True), ops.gemm_nn(a, w, None, torch.float32, split_scratch=True))
-
-
-def _r3_encode_np(x):
-    """CPU restatement of the 3-byte residual code (csrc/common.h r3_encode): T = fp32 pattern rounded half away to 24 bits,
-    hi = (T + 0x80) >> 8 (a bf16 pattern), lo = int8(T - (hi << 8))."""
-    b = x.astype(np.float32).view(np.uint32).astype(np.uint64)
-    hi = (((b + 0x8080) >> 16) & 0xffff).astype(np.uint16)
-    lo = (((b + 0x80) >> 8) & 0xff).astype(np.uint8).view(np.int8)
-    return hi, lo
-
-
-def _r3_decode_np(hi, lo):
-    v = ((hi.astype(np.int64) << 16) + (lo.astype(np.int64) << 8)) & 0xffffffff
-    return v.astype(np.uint32).view(np.float32)
 
 
 def test_resid3_codec_matches_restatement(dev):
