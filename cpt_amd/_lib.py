@@ -115,6 +115,9 @@ _SIGS = {
     "cpt_train_fwd_soft": (C.c_int, [C.POINTER(Model), C.POINTER(SoftTemplate), C.POINTER(Batch), C.POINTER(Outputs), vp, C.c_size_t, vp, BUCKET_CB, vp,
                                      C.POINTER(Dropout)]),
     "cpt_train_bwd_soft": (C.c_int, [C.POINTER(Model), C.POINTER(SoftTemplate), C.POINTER(Batch), C.c_float, vp, vp, C.c_size_t, vp, C.POINTER(Dropout)]),
+    "cpt_train_bwd_from": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(SoftTemplate), C.POINTER(Batch), C.POINTER(ModelGrads), C.c_int, C.c_float, vp,
+                                     vp, C.c_size_t, vp, BUCKET_CB, vp, C.POINTER(Dropout)]),
+    "cpt_train_zero_grads_from": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(ModelGrads), C.c_int, C.c_int, vp]),
     "cpt_train_workspace_bytes": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int, C.c_int]),
     "cpt_train_workspace_bytes_rows": (C.c_size_t, [C.POINTER(Dims), C.c_int, C.c_int, C.c_int, C.c_int]),
     "cpt_train_fwd": (C.c_int, [C.POINTER(Model), C.POINTER(Batch), C.POINTER(Outputs), vp, C.c_size_t, vp]),

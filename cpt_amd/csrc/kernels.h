@@ -56,9 +56,10 @@ int gather_rows(const void* src, int dtype, const int64_t* pos, void* out, int B
                 hipStream_t s, const int64_t* seq = nullptr, int n_seq = 0);      // seq: row b = position pos[b] of sequence seq[b] (of n_seq)
 
 int ce_rows(const float* logits, const int64_t* labels, float* loss, float* dlogits, int R, int V,
-            hipStream_t s, unsigned* ticket = nullptr, float* mean_out = nullptr, float* loss_copy = nullptr);
+            hipStream_t s, unsigned* ticket = nullptr, float* mean_out = nullptr, float* loss_copy = nullptr, float* row_loss = nullptr);
 // ticket (round 6, a word holding 0, left at 0): the LAST workgroup to finish reads the totals back and writes mean_out[0] = sum / count and
 // loss_copy[0..1] = {sum, count} -- no divide kernel on the caller's side, no device-to-device copy of the totals
+// row_loss (with ticket; scratch of 2 R floats): the totals are added up in a fixed order from per-row stores instead of atomics -- same inputs, same bits
 
 int transpose_cast(const void* in, int in_dtype, int ldi, void* out, int out_dtype, int ldo, int R, int C, hipStream_t s);
 int colsum(const void* x, int dtype, int ld, float* out, int R, int C, hipStream_t s);

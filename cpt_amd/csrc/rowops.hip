@@ -1031,9 +1031,41 @@ __device__ __forceinline__ void ce_finish(float* __restrict__ loss, unsigned* __
     *ticket = 0u;
 }
 
+// The same with the totals in a FIXED order (row_loss: scratch of 2 R floats, the training forward's form): every row leaves {its loss, 1} --
+// an ignored row {0, 0} -- in row_loss[2 r ..] with plain stores instead of adding them into loss[] with atomics, whose order of arrival moved
+// the last bits of the loss from run to run; the first wave of the last workgroup to finish adds them up -- lane j the rows j, j + 64, .. in row
+// order, then the wave's butterfly -- and writes loss[0..1], the mean and the copy.  Same inputs, same bits.  All 64 lanes of wave 0 pass here.
+__device__ __forceinline__ void ce_row_out(float* __restrict__ row_loss, int r, float v, float n) {
+    row_loss[2 * (size_t)r] = v; row_loss[2 * (size_t)r + 1] = n;
+}
+__device__ __forceinline__ void ce_finish_rows(float* __restrict__ loss, unsigned* __restrict__ ticket, float* __restrict__ mean_out, float* __restrict__ loss_copy,
+                                               const float* row_loss, int R) {
+    if (!ticket || threadIdx.x >= 64) return;
+    int last = 0;
+    if (threadIdx.x == 0) {
+        __threadfence();
+        last = atomicAdd(ticket, 1u) == gridDim.x - 1 ? 1 : 0;
+    }
+    last = __shfl(last, 0);
+    if (!last) return;
+    __threadfence();
+    float sum = 0.f, cnt = 0.f;
+    for (int r = threadIdx.x; r < R; r += 64) {      // (read at the device's coherence point: other workgroups wrote these)
+        sum += __hip_atomic_load(row_loss + 2 * (size_t)r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        cnt += __hip_atomic_load(row_loss + 2 * (size_t)r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    sum = wave_sum(sum); cnt = wave_sum(cnt);
+    if (threadIdx.x != 0) return;
+    loss[0] = sum; loss[1] = cnt;
+    if (mean_out) mean_out[0] = sum / cnt;
+    if (loss_copy) { loss_copy[0] = sum; loss_copy[1] = cnt; }
+    *ticket = 0u;
+}
+
 __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                       float* __restrict__ loss, float* __restrict__ dlogits, int R, int V,
-                                                      unsigned* __restrict__ ticket, float* __restrict__ mean_out, float* __restrict__ loss_copy) {
+                                                      unsigned* __restrict__ ticket, float* __restrict__ mean_out, float* __restrict__ loss_copy,
+                                                      float* __restrict__ row_loss) {
     __shared__ float red[8];
     const int r = blockIdx.x;
     const long lab = labels[r];
@@ -1041,7 +1073,10 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
     float* d = dlogits ? dlogits + (size_t)r * V : nullptr;
     if (lab < 0 || lab >= V) {            // ignored row: no loss, zero gradient
         if (d) for (int c = threadIdx.x; c < V; c += 256) d[c] = 0.f;
-        ce_finish(loss, ticket, mean_out, loss_copy);
+        if (row_loss) {
+            if (threadIdx.x == 0) ce_row_out(row_loss, r, 0.f, 0.f);
+            ce_finish_rows(loss, ticket, mean_out, loss_copy, row_loss, R);
+        } else ce_finish(loss, ticket, mean_out, loss_copy);
         return;
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1058,11 +1093,16 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
     __syncthreads();
     sum = red[4] + red[5] + red[6] + red[7];
     const float lse = m + logf(sum);
-    if (threadIdx.x == 0) {
-        atomicAdd(&loss[0], lse - x[lab]);
-        atomicAdd(&loss[1], 1.0f);
+    if (row_loss) {
+        if (threadIdx.x == 0) ce_row_out(row_loss, r, lse - x[lab], 1.0f);
+        ce_finish_rows(loss, ticket, mean_out, loss_copy, row_loss, R);
+    } else {
+        if (threadIdx.x == 0) {
+            atomicAdd(&loss[0], lse - x[lab]);
+            atomicAdd(&loss[1], 1.0f);
+        }
+        ce_finish(loss, ticket, mean_out, loss_copy);
     }
-    ce_finish(loss, ticket, mean_out, loss_copy);
     if (d) {
         const float inv = 1.0f / sum;
         for (int c = threadIdx.x; c < V; c += 256) d[c] = expf(x[c] - m) * inv - (c == lab ? 1.f : 0.f);
@@ -1074,7 +1114,8 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const float* __restrict__ 
 constexpr int CE_NV = 32;
 __global__ __launch_bounds__(1024) void ce_rows_reg_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                                            float* __restrict__ loss, float* __restrict__ dlogits, int R, int V,
-                                                           unsigned* __restrict__ ticket, float* __restrict__ mean_out, float* __restrict__ loss_copy) {
+                                                           unsigned* __restrict__ ticket, float* __restrict__ mean_out, float* __restrict__ loss_copy,
+                                                           float* __restrict__ row_loss) {
     __shared__ float red[32];
     const int r = blockIdx.x, tid = threadIdx.x;
     const long lab = labels[r];
@@ -1082,7 +1123,10 @@ __global__ __launch_bounds__(1024) void ce_rows_reg_kernel(const float* __restri
     float* d = dlogits ? dlogits + (size_t)r * V : nullptr;
     if (lab < 0 || lab >= V) {            // ignored row: no loss, zero gradient
         if (d) for (int c = tid; c < V; c += 1024) d[c] = 0.f;
-        ce_finish(loss, ticket, mean_out, loss_copy);
+        if (row_loss) {
+            if (tid == 0) ce_row_out(row_loss, r, 0.f, 0.f);
+            ce_finish_rows(loss, ticket, mean_out, loss_copy, row_loss, R);
+        } else ce_finish(loss, ticket, mean_out, loss_copy);
         return;
     }
     const int lane = tid & 63, w = tid >> 6;
@@ -1109,11 +1153,16 @@ __global__ __launch_bounds__(1024) void ce_rows_reg_kernel(const float* __restri
     sum = 0.f;
 #pragma unroll
     for (int k = 0; k < 16; ++k) sum += red[16 + k];
-    if (tid == 0) {
-        atomicAdd(&loss[0], m + logf(sum) - x[lab]);
-        atomicAdd(&loss[1], 1.0f);
+    if (row_loss) {
+        if (tid == 0) ce_row_out(row_loss, r, m + logf(sum) - x[lab], 1.0f);
+        ce_finish_rows(loss, ticket, mean_out, loss_copy, row_loss, R);
+    } else {
+        if (tid == 0) {
+            atomicAdd(&loss[0], m + logf(sum) - x[lab]);
+            atomicAdd(&loss[1], 1.0f);
+        }
+        ce_finish(loss, ticket, mean_out, loss_copy);
     }
-    ce_finish(loss, ticket, mean_out, loss_copy);
     if (d) {
         const float inv = 1.0f / sum;
 #pragma unroll
@@ -1124,11 +1173,13 @@ __global__ __launch_bounds__(1024) void ce_rows_reg_kernel(const float* __restri
     }
 }
 
-int ce_rows(const float* logits, const int64_t* labels, float* loss, float* dlogits, int R, int V, hipStream_t s, unsigned* ticket, float* mean_out, float* loss_copy) {
+int ce_rows(const float* logits, const int64_t* labels, float* loss, float* dlogits, int R, int V, hipStream_t s, unsigned* ticket, float* mean_out, float* loss_copy,
+            float* row_loss) {
     if (R <= 0 || V <= 0) return CPT_ERR_SHAPE;
     if (!logits || !labels || !loss) return CPT_ERR_NULL;
-    if (V <= CE_NV * 1024) ce_rows_reg_kernel<<<dim3(R), dim3(1024), 0, s>>>(logits, labels, loss, dlogits, R, V, ticket, mean_out, loss_copy);
-    else ce_rows_kernel<<<dim3(R), dim3(256), 0, s>>>(logits, labels, loss, dlogits, R, V, ticket, mean_out, loss_copy);
+    if (row_loss && !ticket) return CPT_ERR_NULL;      // (the fixed-order totals are formed by the ticket's last workgroup)
+    if (V <= CE_NV * 1024) ce_rows_reg_kernel<<<dim3(R), dim3(1024), 0, s>>>(logits, labels, loss, dlogits, R, V, ticket, mean_out, loss_copy, row_loss);
+    else ce_rows_kernel<<<dim3(R), dim3(256), 0, s>>>(logits, labels, loss, dlogits, R, V, ticket, mean_out, loss_copy, row_loss);
     return CPT_OK;
 }
 

@@ -380,6 +380,9 @@ struct TrainFwd : TrainCtx {
     const cpt_outputs* o;
     const float* tmpl; int n_slots;      // soft template (cpt_train_fwd_soft): text ids in (0, n_slots) read their word row from it; NULL for every other call
     unsigned* ce_ticket() const { return (unsigned*)at(w.loss + 16); }      // finish ticket of the cross-entropy launch at the end of the forward
+    // the rows' {loss, 1} pairs of that launch, added up in row order by its last workgroup (2 Rh floats): dt2, [Rh][H] fp32, is a temporary of the
+    // backward's head and idle during the forward.  The loss is then a function of the inputs alone: two runs, the same bits
+    float* ce_row_loss() const { return f32(w.dt2); }
 
     int embed() const {
         bucket(0);
@@ -524,7 +527,7 @@ struct TrainFwd : TrainCtx {
             pin = at(w.t2);
         }
         TRY(gm(CPT_EPI_NONE, pin, H, m->w_rel, H, m->b_rel, nullptr, 0, o->rel, CPT_F32, d.n_rel, B, d.n_rel, H), "gemm(seq_relationship)");
-        TRY(cpt::ce_rows(o->rel, b->labels, o->loss, dlg, B, d.n_rel, s, ce_ticket(), o->loss_mean, f32(w.loss)), "ce_rows(rel)");
+        TRY(cpt::ce_rows(o->rel, b->labels, o->loss, dlg, B, d.n_rel, s, ce_ticket(), o->loss_mean, f32(w.loss), ce_row_loss()), "ce_rows(rel)");
         return CPT_OK;
     }
 
@@ -538,7 +541,7 @@ struct TrainFwd : TrainCtx {
             "gelu+layernorm(head)");
         TRY(gm(CPT_EPI_NONE, t2, H, m->w_dec, H, m->b_dec, nullptr, 0, o->logits, CPT_F32, d.vocab, Rh, d.vocab, H), "gemm(decoder)");
         // (the launch's last workgroup leaves {sum, count} in the workspace for the backward and the mean in o->loss_mean: no memset, copy or divide launch)
-        TRY(cpt::ce_rows(o->logits, b->labels, o->loss, f32(w.dlogits), Rh, d.vocab, s, ce_ticket(), o->loss_mean, f32(w.loss)), "ce_rows");
+        TRY(cpt::ce_rows(o->logits, b->labels, o->loss, f32(w.dlogits), Rh, d.vocab, s, ce_ticket(), o->loss_mean, f32(w.loss), ce_row_loss()), "ce_rows");
         return CPT_OK;
     }
 };
@@ -605,6 +608,13 @@ const LnBwdNames WHAT_LN1 = {"ln_bwd(attn)+dropout+bias", "column-sum jobs (atte
 
 struct TrainBwd : TrainCtx {
     const cpt_rel2* x; const cpt_model_grads* g; float loss_scale; const float* loss_scale_dev;
+    // layer freezing (cpt_train_bwd_from): stages < stage are frozen -- 0 = the full walk; stage - 1 is then the boundary layer, the lowest one with
+    // a parameter gradient (stage = layers + 1: the head alone).  below: a frozen backward goes on under the boundary (soft template), so the data
+    // gradient that leaves the trainable stages is kept; without it nothing reads that gradient and the launch that forms it is left out.
+    int stage; bool below;
+    bool tied_frozen() const { return stage > 0; }                              // the word table (stage 0) is the decoder's weight: no wgrad(decoder)
+    bool head_dx() const { return stage <= d.layers || below; }                 // the head's data gradient into the encoder is read by something
+    bool layer_dx(int l) const { return stage == 0 || l > stage - 1 || below; } // ... and so is layer l's into the rows below it
     // with hidden dropout the gradient that enters a dense layer is the masked one (dmask); the unmasked one (dpre) keeps feeding the residual path
     const float* dpre_f() const { return f32(ph ? w.dmask : w.dpre); }
     const void* dpre_in() const { return dt == CPT_BF16 ? at(ph ? w.dmask_lp : w.dpre_lp) : (const void*)dpre_f(); }
@@ -629,6 +639,7 @@ struct TrainBwd : TrainCtx {
         const void* dpo = dt == CPT_BF16 ? at(w.duh_lp) : (const void*)duh;
         TRY(cpt::colsum(duh, CPT_F32, H, g->b_pool, B, H, s), "colsum(pooler bias)");
         PASS(wgrad(dpo, dt, H, H, at(w.rows), H, H, B, Bp, g->w_pool, H, "wgrad(pooler)"));
+        if (!head_dx()) return CPT_OK;
         return dgrad(dpo, H, H, m->w_pool, H, H, H, B, nullptr, f32(w.drows), CPT_F32, "dgrad(pooler)");
     }
 
@@ -636,11 +647,12 @@ struct TrainBwd : TrainCtx {
         float* dt2 = f32(w.dt2); float* duh = f32(w.duh);
         TRY(cpt::scale_cast(f32(w.dlogits), f32(w.loss), loss_scale, loss_scale_dev, at(w.dl_lp), dt, Rh, V, Vp, s, g->b_dec), "scale(dlogits) + colsum(cls.bias)");
         PASS(dgrad(at(w.dl_lp), Vp, Vp, m->w_dec, H, V, H, Rh, nullptr, dt2, CPT_F32, "dgrad(decoder)"));
-        PASS(wgrad(at(w.dl_lp), dt, Vp, V, at(w.t2), H, H, Rh, Bp, g->word_emb, H, "wgrad(decoder)"));
+        if (!tied_frozen()) PASS(wgrad(at(w.dl_lp), dt, Vp, V, at(w.t2), H, H, Rh, Bp, g->word_emb, H, "wgrad(decoder)"));
         TRY(cpt::ln_bwd(dt2, f32(w.uh), m->tr_ln_g, d.ln_eps, duh, dt == CPT_BF16 ? at(w.duh_lp) : nullptr, dt, g->tr_ln_g,
                         g->tr_ln_b, Rh, H, Rh, 0, 0, 1, s, nullptr, 0, nullptr, g->b_tr), "ln_bwd(head) + transform bias sums");      // (round 6: the bias gradient = column sums of this launch's output, summed inside it)
         const void* duh_in = dt == CPT_BF16 ? at(w.duh_lp) : (const void*)duh;
         PASS(wgrad(duh_in, dt, H, H, at(w.rows), H, H, Rh, Bp, g->w_tr, H, "wgrad(head transform)"));
+        if (!head_dx()) return CPT_OK;
         return dgrad(duh_in, H, H, m->w_tr, H, H, H, Rh, nullptr, f32(w.drows), CPT_F32, "dgrad(head transform)");
     }
 
@@ -688,11 +700,28 @@ struct TrainBwd : TrainCtx {
         else
             PASS(wgrad_pair({dpre_in(), H, LB(l, w.o_ctx), H, gy.w_ao, "wgrad(attn out)"}, {dbig, 3 * H, LB(l, w.o_xin), H, gy.w_qkv, "wgrad(qkv)"}, "wgrad(attn out | qkv)"));
         // (layer 0's result feeds the embedding passes: complete; above that a K-split launch leaves its partial matrices to the next LayerNorm backward)
-        st.dxS = 1;
-        const int rc = dgrad(dbig, 3 * H, 3 * H, y.w_qkv, H, 3 * H, H, M, f32(w.dpre), f32(w.dx), CPT_F32, "dgrad(qkv)+residual", nullptr, nullptr, 0, (fuse_db && l > 0) ? &st.dxS : nullptr, 1);
-        st.dxB = (st.dxS == 2 && M >= 2048) ? 1 : 0;
-        PASS(rc);
+        st.dxS = 1; st.dxB = 0;
+        if (layer_dx(l)) {      // (the boundary layer of a frozen prefix without a template under it: nothing reads this gradient)
+            const int rc = dgrad(dbig, 3 * H, 3 * H, y.w_qkv, H, 3 * H, H, M, f32(w.dpre), f32(w.dx), CPT_F32, "dgrad(qkv)+residual", nullptr, nullptr, 0, (fuse_db && l > 0) ? &st.dxS : nullptr, 1);
+            st.dxB = (st.dxS == 2 && M >= 2048) ? 1 : 0;
+            PASS(rc);
+        }
         if (!fuse_db) bucket(1 + l);
+        return CPT_OK;
+    }
+
+    // What the full walk hands on to the next layer's launches, brought to an end at the boundary of a frozen prefix: the column-sum jobs that wait
+    // for a carrier launch (the boundary layer's attention-side LayerNorm sums) go out on a launch of their own, and so do the K-split partial
+    // matrices of its Q|K|V weight gradient; then the layer's bucket is complete.
+    int flush_boundary(int l, BwdState& st) const {
+        if (st.pend.n > 0) TRY(cpt::col_jobs_flush(st.pend, s), "column-sum jobs (boundary layer)");
+        st.pend = cpt::ColJobs{};
+        if (st.qjob.S > 1) TRY(cpt::reduce_job_flush(st.qjob, s), "partial sums of wgrad(qkv), boundary layer");
+        st.qjob = cpt::ReduceJob{};
+        // (defensive: layer() announces a bucket waiting behind its triple launch before it returns and layer_tail() never sets one, so nothing waits
+        // here today; a later stage function that leaves one must not lose it at the boundary)
+        if (st.ready_after_triple >= 0) { bucket(st.ready_after_triple); st.ready_after_triple = -1; }
+        if (fuse_db) bucket(1 + l);      // (unfused: attention() has announced it)
         return CPT_OK;
     }
 
@@ -819,28 +848,15 @@ struct TrainBwd : TrainCtx {
     }
 };
 
-int train_bwd_impl(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, const cpt_model_grads* g, float loss_scale, const float* loss_scale_dev,
-                   void* workspace, size_t workspace_bytes, void* stream, cpt_bucket_fn grads_ready, void* user, const cpt_dropout* drop) {
-    if (!m || !b || !g || !workspace) return abi_fail(CPT_ERR_NULL, "cpt_train_bwd: null argument");
-    PASS(check_drop(drop, "cpt_train_bwd"));
-    const TrainPlan p = make_train_plan(m, x, b, drop);
-    PASS(check_common(m, b, workspace, workspace_bytes, p, "cpt_train_bwd"));
-    if (p.nsp && b->n_rows > 0) return abi_fail(CPT_ERR_SHAPE, "cpt_train_bwd: label grids (n_rows) belong to the MLM head, not the NSP head");      // (as the forward: Rh has one meaning)
-    if (x && !p.nsp) return abi_fail(CPT_ERR_NULL, "cpt_train_bwd_rel2: the model needs the pooler and head 0 (w_pool, w_rel) and no MLM head");
-    TrainBwd t = {};
-    set_ctx(t, p, m, b, workspace, stream, drop, grads_ready, user);
-    t.x = x; t.g = g; t.loss_scale = loss_scale; t.loss_scale_dev = loss_scale_dev;
-    PASS(p.nsp ? t.head_nsp() : t.head_mlm());
-    if (!p.tail) {      // (pruned last layer: drows IS the gradient of that layer's compact output)
-        hipError_t e = hipMemsetAsync(t.f32(p.w.dx), 0, (size_t)p.M * p.H * 4, t.s);
-        if (e != hipSuccess) return abi_fail(CPT_ERR_HIP - (int)e, "zero dx: %s", hipGetErrorString(e));
-        TRY(cpt::scatter_rows_add(t.f32(p.w.drows), p.nsp ? nullptr : b->mask_pos, t.f32(p.w.dx), p.Rh, p.L, p.H, t.s, b->n_rows > 0 ? b->row_seq : nullptr, p.B), "scatter([MASK] / [CLS] rows)");
-    }
-    t.bucket(m->dims.layers + 1);
-    BwdState st = {};
-    st.ready_after_triple = -1; st.dxS = 1;
-    for (int l = m->dims.layers - 1; l >= 0; --l) PASS(p.tail && l == m->dims.layers - 1 ? t.layer_tail(l, st) : t.layer(l, st));
-    return t.embeddings(st);
+// the head's data gradient enters the encoder: drows scattered into a cleared dx -- once for the three walks below (full, frozen prefix, frozen model).
+// (pruned last layer: drows IS the gradient of that layer's compact output)
+int head_rows_to_dx(const TrainCtx& t) {
+    if (t.tail) return CPT_OK;
+    hipError_t e = hipMemsetAsync(t.f32(t.w.dx), 0, (size_t)t.M * t.H * 4, t.s);
+    if (e != hipSuccess) return abi_fail(CPT_ERR_HIP - (int)e, "zero dx: %s", hipGetErrorString(e));
+    TRY(cpt::scatter_rows_add(t.f32(t.w.drows), t.nsp ? nullptr : t.b->mask_pos, t.f32(t.w.dx), t.Rh, t.L, t.H, t.s, t.b->n_rows > 0 ? t.b->row_seq : nullptr, t.B),
+        "scatter([MASK] / [CLS] rows)");
+    return CPT_OK;
 }
 
 // ---- backward of a frozen model (cpt_train_bwd_soft) ----------------------------------------------------------------------------------------
@@ -973,15 +989,64 @@ int frozen_bwd_impl(const cpt_model* m, const cpt_soft_template* soft, const cpt
     set_ctx(t, p, m, b, workspace, stream, drop, nullptr, nullptr);
     t.soft = soft; t.loss_scale = loss_scale; t.loss_scale_dev = loss_scale_dev;
     PASS(t.head_mlm());
-    if (!p.tail) {      // (pruned last layer: drows IS the gradient of that layer's compact output)
-        hipError_t e = hipMemsetAsync(t.f32(p.w.dx), 0, (size_t)p.M * p.H * 4, t.s);
-        if (e != hipSuccess) return abi_fail(CPT_ERR_HIP - (int)e, "zero dx: %s", hipGetErrorString(e));
-        TRY(cpt::scatter_rows_add(t.f32(p.w.drows), b->mask_pos, t.f32(p.w.dx), p.Rh, p.L, p.H, t.s, b->n_rows > 0 ? b->row_seq : nullptr, p.B), "scatter([MASK] rows)");
-    }
+    PASS(head_rows_to_dx(t));
     BwdState st = {};
     st.ready_after_triple = -1; st.dxS = 1;
     for (int l = m->dims.layers - 1; l >= 0; --l) PASS(p.tail && l == m->dims.layers - 1 ? t.layer_tail(l, st) : t.layer(l, st));
     return t.template_grad();
+}
+
+// ---- the backward walk: the full step, or a frozen prefix of stages (cpt_train_bwd_from) ---------------------------------------------------
+// Stages are the data-parallel buckets: 0 = embedding side, 1 + l = encoder layer l, layers + 1 = pooler and head; stages < first_stage are frozen.
+// ONE walk serves every entry point.  first_stage 0 is the full step: head, every layer, embeddings().  With a frozen prefix the walk runs the same
+// stage functions down to the boundary layer first_stage - 1 and ends what they leave "for the next launch" there (TrainBwd::flush_boundary).
+// Under the boundary: nothing -- or, with a soft template, FrozenBwd's stage functions on the BwdState the boundary layer left (dxS / dxB: its
+// data gradient, possibly still in K-split partial matrices), ending in the template's gradient.  who: the entry point, for error reports.
+int train_bwd_walk(const char* who, const cpt_model* m, const cpt_rel2* x, const cpt_soft_template* soft, const cpt_batch* b, const cpt_model_grads* g, int first_stage,
+                   float loss_scale, const float* loss_scale_dev, void* workspace, size_t workspace_bytes, void* stream, cpt_bucket_fn grads_ready,
+                   void* user, const cpt_dropout* drop) {
+    if (!m || !b || !g || !workspace) return abi_fail(CPT_ERR_NULL, "%s: null argument", who);
+    const int N = m->dims.layers;
+    if (first_stage < 0 || first_stage > N + 1) return abi_fail(CPT_ERR_SHAPE, "%s: first_stage %d outside [0, layers + 1 = %d]", who, first_stage, N + 1);
+    if (soft && first_stage == 0)
+        return abi_fail(CPT_ERR_SHAPE, "%s: a soft template beside a trainable embedding side (first_stage 0) is not supported: the word "
+                        "table's lookup gradient would have to skip the slot ids", who);
+    if (soft && x) return abi_fail(CPT_ERR_SHAPE, "%s: soft-template tuning runs on the MLM head, not on the two relation heads", who);
+    if (soft) PASS(check_soft(m, soft, true, who));
+    if (first_stage <= N && !g->layers) return abi_fail(CPT_ERR_NULL, "%s: g->layers is NULL", who);
+    PASS(check_drop(drop, who));
+    const TrainPlan p = make_train_plan(m, x, b, drop);
+    PASS(check_common(m, b, workspace, workspace_bytes, p, who));
+    if (p.nsp && b->n_rows > 0) return abi_fail(CPT_ERR_SHAPE, "%s: label grids (n_rows) belong to the MLM head, not the NSP head", who);      // (as the forward: Rh has one meaning)
+    if (x && !p.nsp) return abi_fail(CPT_ERR_NULL, "%s: the two-head step needs the pooler and head 0 (w_pool, w_rel) and no MLM head", who);
+    TrainBwd t = {};
+    set_ctx(t, p, m, b, workspace, stream, drop, grads_ready, user);
+    t.x = x; t.g = g; t.loss_scale = loss_scale; t.loss_scale_dev = loss_scale_dev;
+    t.stage = first_stage; t.below = soft != nullptr;
+    PASS(p.nsp ? t.head_nsp() : t.head_mlm());
+    if (!t.head_dx()) {      // the head alone
+        t.bucket(N + 1);
+        return CPT_OK;
+    }
+    PASS(head_rows_to_dx(t));
+    t.bucket(N + 1);
+    BwdState st = {};
+    st.ready_after_triple = -1; st.dxS = 1;
+    const int lb = std::max(first_stage - 1, 0);      // the lowest layer with a parameter gradient (N: none of them has one)
+    for (int l = N - 1; l >= lb; --l) PASS(p.tail && l == N - 1 ? t.layer_tail(l, st) : t.layer(l, st));
+    if (first_stage == 0) return t.embeddings(st);      // the full step: the embedding side's launches carry what layer 0 left
+    if (lb < N) PASS(t.flush_boundary(lb, st));
+    if (!soft) return CPT_OK;
+    FrozenBwd f = {};
+    set_ctx(f, p, m, b, workspace, stream, drop, nullptr, nullptr);
+    f.soft = soft; f.loss_scale = loss_scale; f.loss_scale_dev = loss_scale_dev;
+    for (int l = lb - 1; l >= 0; --l) PASS(p.tail && l == N - 1 ? f.layer_tail(l, st) : f.layer(l, st));
+    return f.template_grad();
+}
+
+int train_bwd_impl(const cpt_model* m, const cpt_rel2* x, const cpt_batch* b, const cpt_model_grads* g, float loss_scale, const float* loss_scale_dev,
+                   void* workspace, size_t workspace_bytes, void* stream, cpt_bucket_fn grads_ready, void* user, const cpt_dropout* drop) {
+    return train_bwd_walk(x ? "cpt_train_bwd_rel2" : "cpt_train_bwd", m, x, nullptr, b, g, 0, loss_scale, loss_scale_dev, workspace, workspace_bytes, stream, grads_ready, user, drop);
 }
 
 }  // namespace
@@ -1008,9 +1073,12 @@ int cpt_train_bwd(const cpt_model* m, const cpt_batch* b, const cpt_model_grads*
 // What cpt_train_bwd needs cleared, in one launch (+ one memset for a table the chosen head does not overwrite): Linear weight
 // gradients are WRITTEN by their GEMMs (and the tied word-embedding table by the decoder's), so only the vectors and small tables
 // that take atomic adds are cleared -- 0.3 MB instead of the 447 MB of a whole-buffer fill per step.
-static int zero_grads_impl(const cpt_model* m, const cpt_rel2* x, const cpt_model_grads* g, int Li, void* stream) {
-    if (!m || !g || !g->layers) return abi_fail(CPT_ERR_NULL, "cpt_train_zero_grads: null argument");
+// first_stage > 0 (cpt_train_zero_grads_from): stages below it are frozen -- nothing of theirs is read through g or cleared
+static int zero_grads_impl(const cpt_model* m, const cpt_rel2* x, const cpt_model_grads* g, int Li, void* stream, int first_stage = 0) {
+    if (!m || !g || (!g->layers && first_stage <= m->dims.layers)) return abi_fail(CPT_ERR_NULL, "cpt_train_zero_grads: null argument");
     const cpt_dims& d = m->dims;
+    if (first_stage < 0 || first_stage > d.layers + 1) return abi_fail(CPT_ERR_SHAPE, "cpt_train_zero_grads_from: first_stage %d outside [0, layers + 1 = %d]", first_stage, d.layers + 1);
+    const bool emb = first_stage == 0;      // the embedding side trains
     hipStream_t s = (hipStream_t)stream;
     const bool nsp = !m->w_tr && !m->w_dec;
     const size_t H = d.hidden, I = d.inter;
@@ -1027,9 +1095,11 @@ static int zero_grads_impl(const cpt_model* m, const cpt_rel2* x, const cpt_mode
         hipError_t e = hipMemsetAsync(p, 0, n * 4, s);
         return e == hipSuccess ? CPT_OK : abi_fail(CPT_ERR_HIP - (int)e, "cpt_train_zero_grads: %s", hipGetErrorString(e));
     };
-    seg(g->pos_emb, (size_t)d.max_pos * H); seg(g->type_emb, (size_t)d.type_vocab * H);
-    seg(g->emb_ln_g, H); seg(g->emb_ln_b, H); seg(g->b_img, H); seg(g->img_ln_g, H); seg(g->img_ln_b, H);
-    for (int l = 0; l < d.layers; ++l) {
+    if (emb) {
+        seg(g->pos_emb, (size_t)d.max_pos * H); seg(g->type_emb, (size_t)d.type_vocab * H);
+        seg(g->emb_ln_g, H); seg(g->emb_ln_b, H); seg(g->b_img, H); seg(g->img_ln_g, H); seg(g->img_ln_b, H);
+    }
+    for (int l = std::max(first_stage - 1, 0); l < d.layers; ++l) {
         const cpt_layer_grads& y = g->layers[l];
         seg(y.b_qkv, 3 * H); seg(y.b_ao, H); seg(y.ln1_g, H); seg(y.ln1_b, H);
         seg(y.b_in, I); seg(y.b_out, H); seg(y.ln2_g, H); seg(y.ln2_b, H);
@@ -1040,12 +1110,12 @@ static int zero_grads_impl(const cpt_model* m, const cpt_rel2* x, const cpt_mode
     if (ovf) return abi_fail(CPT_ERR_SHAPE, "cpt_train_zero_grads: more than %d gradient vectors (layers = %d)", cpt::ZS_MAX, d.layers);
     TRY(cpt::zero_segments(z, s), "zero_segments");
     if (nsp) {      // no decoder GEMM writes the word table: the lookup gradient adds into it
-        PASS(big(g->word_emb, (size_t)d.vocab * H));
+        if (emb) PASS(big(g->word_emb, (size_t)d.vocab * H));
         PASS(big(g->w_tr, H * H));
     }
     // (the MLM path leaves the pooler / relation head without a gradient: nothing writes those regions of the caller's gradient buffer and the
     // optimizer skips them (code 0) -- round 6: no per-step fill of them either)
-    if (Li <= 0) PASS(big(g->w_img, H * (size_t)d.img_dim));      // no regions: the projection gets no gradient
+    if (Li <= 0 && emb) PASS(big(g->w_img, H * (size_t)d.img_dim));      // no regions: the projection gets no gradient
     return CPT_OK;
 }
 
@@ -1157,6 +1227,18 @@ int cpt_train_fwd_soft(const cpt_model* m, const cpt_soft_template* st, const cp
 int cpt_train_bwd_soft(const cpt_model* m, const cpt_soft_template* st, const cpt_batch* b, float loss_scale, const float* loss_scale_dev,
                        void* workspace, size_t workspace_bytes, void* stream, const cpt_dropout* drop) {
     return frozen_bwd_impl(m, st, b, loss_scale, loss_scale_dev, workspace, workspace_bytes, stream, drop);
+}
+
+int cpt_train_bwd_from(const cpt_model* m, const cpt_rel2* x, const cpt_soft_template* soft, const cpt_batch* b, const cpt_model_grads* g, int first_stage,
+                       float loss_scale, const float* loss_scale_dev, void* workspace, size_t workspace_bytes, void* stream, cpt_bucket_fn grads_ready,
+                       void* user, const cpt_dropout* drop) {
+    if (!m || !b) return abi_fail(CPT_ERR_NULL, "cpt_train_bwd_from: null argument");
+    if (x) PASS(check_rel2(m, x, b, "cpt_train_bwd_from", stream, false));
+    return train_bwd_walk("cpt_train_bwd_from", m, x, soft, b, g, first_stage, loss_scale, loss_scale_dev, workspace, workspace_bytes, stream, grads_ready, user, drop);
+}
+
+int cpt_train_zero_grads_from(const cpt_model* m, const cpt_rel2* x, const cpt_model_grads* g, int first_stage, int Li, void* stream) {
+    return zero_grads_impl(m, x, g, Li, stream, first_stage);
 }
 
 }  // extern "C"

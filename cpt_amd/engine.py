@@ -91,6 +91,8 @@ class PackedModel(object):
         self._fold_stale = True
         self.pending = None         # data-parallel optimizer whose parameter all-gather is still in flight (train.FusedAdamW)
         self.last_shape = None      # (B, Lt, Li) the last inference forward ran on: the padded shape, or what trim=True cut it to
+        self.first_stage = None     # layer freezing (train.freeze_layers ..): stages < this are frozen; None = no stage set, the full step
+        self.stage_pattern = None   # ... and the (name, parameter, stage, checked) list the training forward holds the requires_grad flags to
         self.last_train_shape = None    # (B, Lt, Li) the last training forward ran on (train.py; cut by a driver's trim=True or model.trim_training)
 
     # ---- packing -------------------------------------------------------------------------

@@ -67,8 +67,10 @@ class REC_MLM_CPT(_EngineMixin, BertPreTrainedModel):
         if vocab_columns is not None and (not rows or masked_lm_labels is not None):
             raise NotImplementedError("cpt_amd: vocab_columns goes with mask_token_pos and without masked_lm_labels")
         # a frozen model with a trainable soft template (cpt_amd/soft_prompt.py) trains too: the frozen step
-        soft = torch.is_grad_enabled() and masked_lm_labels is not None and frozen_step(self)
-        if torch.is_grad_enabled() and masked_lm_labels is not None and (soft or self.bert.img_embedding.weight.requires_grad):
+        # ... and so does one with a stage set (train.freeze_layers ..: the region projection is then frozen, the head never is)
+        staged = torch.is_grad_enabled() and masked_lm_labels is not None and bool(self._engine().first_stage)
+        soft = torch.is_grad_enabled() and masked_lm_labels is not None and not staged and frozen_step(self)
+        if torch.is_grad_enabled() and masked_lm_labels is not None and (soft or staged or self.bert.img_embedding.weight.requires_grad):
             from .train import mlm_loss_with_grad
             if self.trim_training and mask_token_pos is None and masked_lm_labels.dim() == 2:
                 # length-aware training on the reference call form: the extents come from the mask AND the label grid, the grid is cut with the batch

@@ -12,8 +12,12 @@ the template takes the frozen step: cpt_train_fwd_soft / cpt_train_bwd_soft, the
 no 447 MB gradient buffer, no optimizer state for the model.  ``loss.backward()`` leaves ``template_embeddings.weight.grad`` as a
 (n_slots, H) fp32 tensor (added to an existing one, as autograd accumulates); any torch optimizer over that one tensor works.
 
-Limits: the MLM head only (``REC_MLM_CPT``; one [MASK] row per sequence or a label grid); a trainable template together with a
-trainable backbone, and the NSP-CPT heads in training, raise NotImplementedError.
+With a trainable stage set (``train.freeze_layers`` ..: the embedding side and the lower layers frozen, the top layers and the head
+trainable) a trainable template is accepted as well: attach it with ``freeze_backbone=False``, set the stage; the backward trains the top
+stages and goes on below the boundary as the frozen step, ending in the template's gradient (include/cpt_hip.h cpt_train_bwd_from).
+
+Limits: the MLM head only (``REC_MLM_CPT``; one [MASK] row per sequence or a label grid); a trainable template beside a backbone that
+trains from the embeddings up (no stage set), and the NSP-CPT heads in training, raise NotImplementedError.
 """
 import torch
 from torch import nn
@@ -81,8 +85,9 @@ def attach_from_state_dict(model, state_dict):
 
 def frozen_step(model):
     """True when a training forward of ``model`` takes the frozen step: a template is attached and it is the only parameter that
-    requires grad.  A trainable template beside a trainable backbone raises NotImplementedError; a template that does not require
-    grad leaves training as it is without one (the forward still substitutes its rows)."""
+    requires grad.  A trainable template beside a trainable backbone raises NotImplementedError (train.mlm_loss_with_grad does not ask
+    when a stage >= 1 is set: the template then trains under the trainable top stages); a template that does not require grad leaves
+    training as it is without one (the forward still substitutes its rows)."""
     t = template_of(model)
     if t is None or not t.requires_grad:
         return False

@@ -134,12 +134,109 @@ def _state(eng):
     return st
 
 
-def _named_grad_views(eng, st):
+# ---- layer freezing: train the top stages and the head ------------------------------------------------------------------------------------
+# A stage is a data-parallel bucket (engine.bucket_of): 0 = the embedding tables, embeddings.LayerNorm and the region projection (+ its LayerNorm),
+# 1 + l = encoder layer l, N + 1 = pooler and task head.  ``first_stage = s`` (kept on the engine) freezes the stages < s: the backward stops at
+# the boundary (include/cpt_hip.h cpt_train_bwd_from), AdamW and the data-parallel traffic cover the trainable buckets only.  The tied decoder
+# weight IS the word table (one Parameter, stage 0): every s >= 1 freezes it, while cls.bias and the head transform stay trainable.
+
+def first_stage_of(eng):
+    """The engine's recorded stage; 0 = none set (the full step, ``requires_grad`` flags ignored)."""
+    return int(getattr(eng, "first_stage", None) or 0)
+
+
+def trainable_stage(model):
+    """The stage set by freeze_layers / freeze_embeddings / train_head_only (0: none; everything trains)."""
+    return first_stage_of(model._engine())
+
+
+def stage_of_parameter(eng, name):
+    """Stage (= data-parallel bucket) of the engine parameter ``name``."""
+    from .engine import bucket_of
+    return bucket_of(name, eng.cfg.num_hidden_layers)
+
+
+def trainable_range(buckets, stage):
+    """[lo, hi) of the flat parameter / gradient / moment buffers that stages >= ``stage`` occupy (buckets: engine.bucket_table's)."""
+    ks = sorted(buckets)
+    return buckets[stage][0] if stage > 0 else 0, buckets[ks[-1]][1]
+
+
+def trainable_buckets(buckets, stage):
+    """The data-parallel buckets of the stages >= ``stage``."""
+    return {k: v for k, v in buckets.items() if k >= stage}
+
+
+def _set_stage(model, s):
+    eng = model._engine()
+    nl = eng.cfg.num_hidden_layers
+    s = int(s)
+    if not 0 <= s <= nl + 1:
+        raise ValueError("cpt_amd: stage %d outside [0, num_hidden_layers + 1 = %d]" % (s, nl + 1))
+    skip = no_grad_prefixes(eng.head)
+    pattern = []          # (name, parameter, its stage, checked by check_stage_flags): kept on the engine, a training forward walks it on the host
+    for n, p in eng._named().items():
+        k = stage_of_parameter(eng, n)
+        p.requires_grad_(k >= s)
+        if k < s:
+            p.grad = None
+        pattern.append((n, p, k, not (skip and n.startswith(skip))))
+    eng.first_stage = s if s > 0 else None
+    eng.stage_pattern = pattern if s > 0 else None
+    st = _state(eng)
+    if st.grad is not None and s > 0 and getattr(eng, "buckets", None):
+        st.grad[:trainable_range(eng.buckets, s)[0]].zero_()      # frozen ranges of the flat gradient hold zeros (the clips read the whole buffer)
+    return s
+
+
+def freeze_layers(model, k):
+    """Freeze the embedding side and encoder layers 0 .. k - 1 (stage 1 + k): layers k .. N - 1, the pooler and the head train."""
+    k = int(k)
+    if not 0 <= k <= model._engine().cfg.num_hidden_layers:
+        raise ValueError("cpt_amd: freeze_layers(k): k outside [0, num_hidden_layers]")
+    return _set_stage(model, 1 + k)
+
+
+def freeze_embeddings(model):
+    """Freeze the embedding side (stage 1): the word, position and token-type tables (the tied decoder weight with the word table),
+    embeddings.LayerNorm, the region projection and its LayerNorm.  Wider than the reference launch scripts' --freeze_embedding, which is
+    documented for the word embeddings alone: only a prefix of whole stages can be frozen."""
+    return _set_stage(model, 1)
+
+
+def train_head_only(model):
+    """Freeze everything but the pooler and the task head (stage N + 1)."""
+    return _set_stage(model, model._engine().cfg.num_hidden_layers + 1)
+
+
+def unfreeze(model):
+    """Every parameter trains again (stage 0); ``requires_grad`` flags are ignored again, as without a stage.  Like every stage call it
+    WRITES the flag of every engine parameter: a flag switched off by hand before any stage was set (which the step ignored) comes back on."""
+    return _set_stage(model, 0)
+
+
+def check_stage_flags(model):
+    """With a stage set, the parameters' ``requires_grad`` flags must BE that prefix pattern: a flag changed by hand since (a frozen middle
+    layer, a trainable word table above a frozen embedding side) would silently train something else.  Parameters outside the loss's graph
+    (no_grad_prefixes) are not looked at."""
+    eng = model._engine()
+    s = first_stage_of(eng)
+    if s == 0:
+        return
+    for n, p, k, checked in eng.stage_pattern:
+        if checked and p.requires_grad != (k >= s):
+            raise NotImplementedError("cpt_amd: stage %d is set (stages < %d frozen) but parameter %s (stage %d) has requires_grad=%s: only a frozen "
+                                      "PREFIX of stages is implemented -- set it with freeze_layers / freeze_embeddings / train_head_only / unfreeze"
+                                      % (s, s, n, k, bool(p.requires_grad)))
+
+
+def _named_grad_views(eng, st, stage=0):
     named = eng._named()
     out = []
     skip = no_grad_prefixes(eng.head)
+    frozen = {n for n, _, k, _ in eng.stage_pattern if k < stage} if stage else ()
     for n, p in named.items():
-        if skip and n.startswith(skip):
+        if (skip and n.startswith(skip)) or n in frozen:
             out.append((p, None))
         else:
             off, num = eng.offsets[n]
@@ -160,8 +257,12 @@ def rel2_desc(eng, st, B0, labels_host=None, score=None):
 
 class _MLMLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, trigger, eng, tensors, drop, rel2=None):
+    def forward(ctx, trigger, eng, tensors, drop, rel2=None, tmpl=None):
+        # tmpl (stage >= 1 only): the trainable soft template beside the trainable top stages -- the second differentiable input
         ctx.eng = eng
+        ctx.stage = first_stage_of(eng)
+        ctx.soft = tmpl is not None
+        ctx.tmpl_version = tmpl._version if tmpl is not None else None
         st = _state(eng)
         ids, seg, mask, pos, feats, mpos, labels, rseq = tensors
         B, Lt = ids.shape
@@ -201,6 +302,10 @@ class _MLMLoss(torch.autograd.Function):
             x = rel2_desc(eng, st, B0, labels_host)
             L.check(L.lib().cpt_train_fwd_rel2(C.byref(m), C.byref(x), C.byref(bt), C.byref(o), ws.data_ptr(), ws.numel(), L.stream_ptr(),
                                                cb, None, C.byref(drop) if drop is not None else None), "cpt_train_fwd_rel2")
+        elif tmpl is not None:
+            soft = eng.soft_template()
+            L.check(L.lib().cpt_train_fwd_soft(C.byref(m), C.byref(soft), C.byref(bt), C.byref(o), ws.data_ptr(), ws.numel(), L.stream_ptr(),
+                                               cb, None, C.byref(drop) if drop is not None else None), "cpt_train_fwd_soft")
         else:
             L.check(L.lib().cpt_train_fwd_ex(C.byref(m), C.byref(bt), C.byref(o), ws.data_ptr(), ws.numel(), L.stream_ptr(),
                                              cb, None, C.byref(drop) if drop is not None else None), "cpt_train_fwd")
@@ -226,20 +331,28 @@ class _MLMLoss(torch.autograd.Function):
             raise RuntimeError("cpt_amd: backward of a stale training forward: the engine keeps the activations of the LATEST "
                                "training forward only (one workspace per model); call backward() before the next "
                                "training forward of the same model")
+        stage = ctx.stage
+        if stage != first_stage_of(eng):
+            raise RuntimeError("cpt_amd: the trainable stage was changed between a training forward and its backward")
         st.ensure()
         m, _ = eng.descriptor(train=True)
-        views = _named_grad_views(eng, st)
+        views = _named_grad_views(eng, st, stage)
         accumulate = any(p.grad is not None for p, v in views if v is not None)
         if st.sync is not None:
             st.sync.begin_backward()      # reduce-scatters of an unconsumed earlier backward may still read st.grad: wait BEFORE touching it
+        live = st.grad[trainable_range(eng.buckets, stage)[0]:]       # the trainable stages' range (stage 0: all of it)
         if accumulate:
-            keep = st.grad.clone()
+            keep = live.clone()
         g, _ = st.gdesc
         x, _ = getattr(st, "saved_rel2", (None, None))
         if x is not None:
             x = rel2_desc(eng, st, x.B0)      # (the gradient buffer may have been made after the forward)
         # only what the backward ADDS into (bias / LayerNorm vectors, small tables) is cleared; weight gradients are written whole
-        if x is not None:
+        g_tmpl = None
+        if stage > 0:
+            L.check(L.lib().cpt_train_zero_grads_from(C.byref(m), C.byref(x) if x is not None else None, C.byref(g), stage, int(bt.Li), L.stream_ptr()),
+                    "cpt_train_zero_grads_from")
+        elif x is not None:
             L.check(L.lib().cpt_train_zero_grads_rel2(C.byref(m), C.byref(x), C.byref(g), int(bt.Li), L.stream_ptr()), "cpt_train_zero_grads_rel2")
         else:
             L.check(L.lib().cpt_train_zero_grads(C.byref(m), C.byref(g), int(bt.Li), L.stream_ptr()), "cpt_train_zero_grads")
@@ -255,7 +368,20 @@ class _MLMLoss(torch.autograd.Function):
                 errs.append(e)
         cb = L.BUCKET_CB(grads_ready) if sync is not None else L.NULL_CB     # (None: buckets are reduced in optimizer.step())
         gl = grad_loss.to(torch.float32).contiguous()          # device scalar: no host synchronisation between fwd and bwd
-        if x is not None:
+        if stage > 0:
+            soft = None
+            if ctx.soft:
+                from .soft_prompt import template_of
+                tmpl = template_of(eng.module)
+                if tmpl is None or tmpl._version != ctx.tmpl_version:
+                    raise RuntimeError("cpt_amd: the soft template was detached or written between the training forward and its backward")
+                g_tmpl = torch.empty_like(tmpl)          # written whole by the backward
+                soft = eng.soft_template(grad=g_tmpl)
+            L.check(L.lib().cpt_train_bwd_from(C.byref(m), C.byref(x) if x is not None else None, C.byref(soft) if soft is not None else None, C.byref(bt),
+                                               C.byref(g), stage, 1.0, gl.data_ptr(), st.ws.data_ptr(), st.ws.numel(), L.stream_ptr(), cb, None,
+                                               C.byref(drop) if drop is not None else None),
+                    "cpt_train_bwd_from")
+        elif x is not None:
             L.check(L.lib().cpt_train_bwd_rel2(C.byref(m), C.byref(x), C.byref(bt), C.byref(g), 1.0, gl.data_ptr(), st.ws.data_ptr(), st.ws.numel(),
                                                L.stream_ptr(), cb, None, C.byref(drop) if drop is not None else None), "cpt_train_bwd_rel2")
         else:
@@ -264,7 +390,7 @@ class _MLMLoss(torch.autograd.Function):
         if errs:
             raise errs[0]
         if accumulate:
-            st.grad.add_(keep)
+            live.add_(keep)
             if st.sync is not None and not st.defer:
                 # the closing micro-step of an accumulation window: the sum is final now -- start every bucket's reduce-scatter here
                 # (it then runs under whatever the caller does before step(); nothing of this backward was left to hide it under)
@@ -280,7 +406,12 @@ class _MLMLoss(torch.autograd.Function):
             st.sent_version = st.grad._version
         st.saved = None
         st.saved_rel2 = (None, None)
-        return None, None, None, None, None
+        if g_tmpl is not None:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                dist.all_reduce(g_tmpl)          # the template's averaging all-reduce, as in the frozen step
+                g_tmpl.div_(dist.get_world_size())
+        return None, None, None, None, None, g_tmpl
 
 
 class _SoftTemplateLoss(torch.autograd.Function):
@@ -416,6 +547,7 @@ def mlm_loss_with_grad(model, input_ids, token_type_ids, attention_mask, labels,
     (trim_training_batch: one small synchronisation); the step then runs unchanged on (B, Lt' + Li').  ``eng.last_train_shape`` is the
     (B, Lt', Li') that ran."""
     eng = model._engine()
+    check_stage_flags(model)           # (with a stage set the flags must be its prefix pattern; without one they are ignored)
     if (rel2 is not None) != (eng.head == "qar"):
         raise RuntimeError("cpt_amd: the two-head step (rel2) belongs to the VCR Q->AR model and it alone")
     if mask_token_pos is None and eng.head not in ("nsp", "qar"):
@@ -427,8 +559,13 @@ def mlm_loss_with_grad(model, input_ids, token_type_ids, attention_mask, labels,
     if eng.pending is None:          # (data parallel: a pending parameter all-gather is awaited bucket by bucket in the forward)
         eng.refresh_shadow(train=True)
     from .soft_prompt import frozen_step, template_of
-    soft = frozen_step(model)          # (raises for a trainable template beside a trainable backbone)
-    if not soft and template_of(model) is not None:
+    stage = first_stage_of(eng)
+    tmpl = template_of(model)
+    joint = stage > 0 and tmpl is not None and tmpl.requires_grad       # a trainable template under trainable top stages
+    if joint and eng.head != "cpt":
+        raise NotImplementedError("cpt_amd: a soft template trains on REC_MLM_CPT (head 'cpt'), not head '%s'" % eng.head)
+    soft = (not joint) and frozen_step(model)          # (raises for a trainable template beside a backbone that trains from stage 0)
+    if not soft and not joint and tmpl is not None:
         raise NotImplementedError("cpt_amd: training the backbone of a model with a soft template attached is not implemented (the full "
                                   "backward knows nothing of the substituted rows): detach the template or train it alone")
     if soft and rel2 is not None:
@@ -458,7 +595,9 @@ def mlm_loss_with_grad(model, input_ids, token_type_ids, attention_mask, labels,
     trigger = getattr(st, "trigger", None)      # one leaf per engine, made once: autograd needs an input that requires grad, backward returns None for it
     if trigger is None or trigger.device != eng.flat.device:
         trigger = st.trigger = torch.zeros((), device=eng.flat.device, requires_grad=True)
-    if rel2 is not None:
+    if joint:
+        loss, logits = _MLMLoss.apply(trigger, eng, tensors, dropout_for(model, st), None, tmpl)
+    elif rel2 is not None:
         loss, logits = _MLMLoss.apply(trigger, eng, tensors, dropout_for(model, st), rel2)
     else:
         loss, logits = _MLMLoss.apply(trigger, eng, tensors, dropout_for(model, st))
@@ -536,6 +675,7 @@ class FusedAdamW(object):
         self.sync = None
         self._clip = 1.0
         self._stale_shadow = set()
+        self._stage = None          # the trainable stage the moments / shards were laid out for (bound at the first use, fixed once step() has run)
         import torch.distributed as dist
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
         self.dp = self.world > 1 or self.force_collectives
@@ -561,13 +701,35 @@ class FusedAdamW(object):
                 return False
         return _NoSync()
 
+    def _check_stage(self):
+        """Layer freezing: the update covers the stages >= the engine's stage.  The stage is bound when the optimizer first lays out its state
+        and may still change until step() has run once; afterwards the moments (and, data parallel, the shard layout both ranks agreed on)
+        belong to that stage."""
+        cur = first_stage_of(self.eng)
+        if self._stage is not None and cur != self._stage:
+            if self.step_count > 0:
+                raise RuntimeError("cpt_amd: the trainable stage changed from %d to %d after this optimizer has stepped: its moments and gradient "
+                                   "shards are laid out for stage %d -- build a new optimizer" % (self._stage, cur, self._stage))
+            self.sync = None            # nothing applied yet: lay the state out again for the new stage
+            self.m = self.v = self.code = None
+            _state(self.eng).sync = None
+        self._stage = cur
+        return cur
+
+    def trainable_elements(self):
+        """(lo, hi) of the flat buffers that step() updates (world size 1: one AdamW launch over it)."""
+        self.eng.ensure_packed()
+        return trainable_range(self.eng.buckets, self._check_stage())
+
     def _ensure(self):
         eng = self.eng
+        stage = self._check_stage()
         eng.ensure_packed()
         dev = eng.flat.device
         if self.dp and (self.sync is None or self.sync.device != dev):
             from . import dist as cdist
-            self.sync = cdist.ShardedGradSync(eng.buckets, dev, wire=self.grad_wire, force_collectives=self.force_collectives)
+            # (frozen stages take no part: no gradient shard, no reduce-scatter, no AdamW, no parameter all-gather -- their bf16 shadow never goes stale)
+            self.sync = cdist.ShardedGradSync(trainable_buckets(eng.buckets, stage), dev, wire=self.grad_wire, force_collectives=self.force_collectives)
             cdist.broadcast_(eng.flat, 0)             # replicas start from rank 0's parameters
             eng.weights_updated()
             _state(eng).sync = self.sync
@@ -670,6 +832,7 @@ class FusedAdamW(object):
 
     def step(self):
         eng = self.eng
+        self._check_stage()          # (first: a stage changed behind a stepped optimizer raises before anything is touched)
         self._ensure()
         st = _state(eng)
         if st.grad is None:
@@ -679,9 +842,10 @@ class FusedAdamW(object):
         wd = self.param_groups[2]["weight_decay"]
         lp = eng.dtype == "bf16" and eng.flat_lp is not None
         if self.sync is None:
-            shadow = eng.flat_lp.data_ptr() if lp else None
-            self._adamw(eng.flat.data_ptr(), st.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.code.data_ptr(), shadow,
-                        eng.flat.numel(), lr, wd, self._clip)
+            lo, hi = trainable_range(eng.buckets, self._stage)        # (stage 0: the whole buffer; frozen stages keep parameters, moments and shadow)
+            shadow = eng.flat_lp.data_ptr() + lo * 2 if lp else None
+            self._adamw(eng.flat.data_ptr() + lo * 4, st.grad.data_ptr() + lo * 4, self.m.data_ptr() + lo * 4, self.v.data_ptr() + lo * 4,
+                        self.code.data_ptr() + lo, shadow, hi - lo, lr, wd, self._clip)
             self._clip = 1.0
             eng.weights_updated(shadow_fresh=shadow is not None)
             return

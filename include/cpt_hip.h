@@ -475,6 +475,33 @@ int cpt_train_fwd_soft(const cpt_model* m, const cpt_soft_template* st, const cp
 int cpt_train_bwd_soft(const cpt_model* m, const cpt_soft_template* st, const cpt_batch* b, float loss_scale, const float* loss_scale_dev,
                        void* workspace, size_t workspace_bytes, void* stream, const cpt_dropout* drop);
 
+/* ------------------------------------------------------------------------------------------
+ * Layer freezing: the training step with a frozen PREFIX of stages.  A stage is a data-parallel bucket (above): 0 = the embedding tables,
+ * embeddings.LayerNorm and the region projection (+ its LayerNorm), 1 + l = encoder layer l, layers + 1 = pooler and task head.
+ * first_stage = s: stages < s are frozen.  s = 0 IS cpt_train_bwd_ex / cpt_train_bwd_rel2 / cpt_train_zero_grads(_rel2) (the same code path);
+ * s = 1 freezes the embedding side, s = 1 + k also layers 0 .. k - 1, s = layers + 1 trains the head alone.  Added beside ABI 8, no struct changed.
+ * The FORWARD is unchanged -- cpt_train_fwd_ex / cpt_train_fwd_rel2 / cpt_train_fwd_soft, same workspace (the frozen stages' activations are
+ * still kept) -- and all three heads are served: MLM (mask_pos or a label grid), NSP, and VCR Q->AR through x (NULL otherwise).
+ *   The walk: head, then the layers layers - 1 .. s - 1 exactly as cpt_train_bwd_ex runs them, then it STOPS.  At the stop, what a layer leaves to
+ *     the next layer's launches -- column sums waiting for a carrier launch, K-split partial matrices of the Q|K|V weight gradient -- goes out on
+ *     launches of its own; the boundary layer's data gradient into the rows below (dgrad(qkv) + residual) is not formed, and with s = layers + 1
+ *     neither is the head's.  No embedding-side launch runs for s >= 1.
+ *   The tied decoder weight is the word table, stage 0: for every s >= 1 it is frozen -- wgrad(decoder) is not launched and no lookup gradient
+ *     exists; cls.bias (b_dec), the transform dense and its LayerNorm stay trainable.  A trainable word table above a frozen embedding side
+ *     cannot be expressed.
+ *   soft (NULL otherwise; MLM head, s >= 1): the walk keeps the boundary data gradient and continues BELOW the boundary as cpt_train_bwd_soft runs
+ *     a frozen model (data-gradient chain only), ending in soft->g_tmpl (written whole, same bits for the same inputs).  soft with s = 0 is
+ *     CPT_ERR_SHAPE: the word table's lookup gradient would have to skip the slot ids.
+ * WRITE contract: nothing that belongs to a frozen stage is written OR READ through g -- its pointers (word_emb .. img_ln_b, layers[l] for
+ *   l < s - 1; g->layers itself with s = layers + 1) may be NULL.  Trainable stages keep the write / accumulate split of cpt_train_bwd.
+ *   grads_ready fires for the buckets layers + 1 .. s only, in that order.  cpt_train_zero_grads_from clears only the trainable stages'
+ *   accumulate targets (Li is read with s = 0 only).
+ * ---------------------------------------------------------------------------------------- */
+int cpt_train_bwd_from(const cpt_model* m, const cpt_rel2* x, const cpt_soft_template* soft, const cpt_batch* b, const cpt_model_grads* g, int first_stage,
+                       float loss_scale, const float* loss_scale_dev, void* workspace, size_t workspace_bytes, void* stream, cpt_bucket_fn grads_ready,
+                       void* user, const cpt_dropout* drop);
+int cpt_train_zero_grads_from(const cpt_model* m, const cpt_rel2* x, const cpt_model_grads* g, int first_stage, int Li, void* stream);
+
 /* torch.optim.AdamW update (fewshot/refcoco_cpt.py:343,249) over flat buffers of n fp32 elements
  * (n % 4 == 0).  code[i]: 0 = no gradient on this path (skipped), 1 = weight decay, 2 = no decay
  * (fewshot/refcoco_cpt.py:320-338).  grad is multiplied by grad_scale first (1/world after a
