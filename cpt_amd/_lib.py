@@ -83,6 +83,12 @@ class Rel2(C.Structure):
     _fields_ = [("B0", C.c_int32)] + [(n, C.c_void_p) for n in ("w_rel1", "b_rel1", "g_w_rel1", "g_b_rel1", "score", "labels_host")]
 
 
+class ResidentStore(C.Structure):
+    """cpt_resident_store: the device tables of an evaluation set (cpt_amd/resident.py)."""
+    _fields_ = [(n, C.c_void_p) for n in ("feats", "ids", "seg", "mask", "mask_pos", "feat_block", "block_rows", "block_off")] + \
+               [("n_rows", C.c_int64)] + [(n, C.c_int32) for n in ("feat_dtype", "pitch", "img_dim", "Lt", "Li", "n_seq", "seq_base", "n_blocks")]
+
+
 _SIGS = {
     "cpt_version": (C.c_int, []),
     "cpt_last_error": (C.c_char_p, []),
@@ -105,6 +111,7 @@ _SIGS = {
     "cpt_trim_batch": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "cpt_train_extents": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
     "cpt_trim_batch_labels": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
+    "cpt_gather_batch": (C.c_int, [C.POINTER(ResidentStore), vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "cpt_train_fwd_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(Batch), C.POINTER(Outputs), vp, C.c_size_t, vp, BUCKET_CB, vp,
                                      C.POINTER(Dropout)]),
     "cpt_train_bwd_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(Batch), C.POINTER(ModelGrads), C.c_float, vp, vp, C.c_size_t, vp,

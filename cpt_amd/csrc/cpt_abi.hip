@@ -1171,4 +1171,15 @@ int cpt_trim_batch_labels(const int64_t* input_ids, const int64_t* token_type, c
                      "cpt_trim_batch_labels");
 }
 
+int cpt_gather_batch(const cpt_resident_store* store, const int32_t* seq_idx, int B, int Lt_out, int Li_out, int64_t* input_ids_out,
+                     int64_t* token_type_out, int64_t* attn_mask_out, int64_t* mask_pos_out, float* img_feats_out, void* stream) {
+    if (!store || !seq_idx || !input_ids_out || !token_type_out || !attn_mask_out || (Li_out > 0 && !img_feats_out))
+        return abi_fail(CPT_ERR_NULL, "cpt_gather_batch: null argument");
+    if (B <= 0 || Lt_out <= 0 || Lt_out > store->Lt || Li_out < 0 || Li_out > store->Li || store->n_seq <= 0 || (Li_out > 0 && store->img_dim <= 0))
+        return abi_fail(CPT_ERR_SHAPE, "cpt_gather_batch: B %d, %d + %d -> %d + %d, img_dim %d, %d sequences", B, store->Lt, store->Li, Lt_out, Li_out,
+                        store->img_dim, store->n_seq);
+    return abi_check(cpt::gather_batch(store, seq_idx, B, Lt_out, Li_out, input_ids_out, token_type_out, attn_mask_out, mask_pos_out, img_feats_out,
+                                       (hipStream_t)stream), "cpt_gather_batch");
+}
+
 }  // extern "C"

@@ -326,5 +326,8 @@ int trim_batch(const int64_t* ids, const int64_t* type, const int64_t* pos, cons
                const int64_t* lab = nullptr, int64_t* lab_o = nullptr);      // (lab: the label grid of cpt_trim_batch_labels)
 // trim.hip, training: extents of a mask with a label grid or labelled positions, one workgroup and no atomics (cpt_train_extents)
 int train_extents(const int64_t* mask, int B, int Lt, int Li, const int64_t* grid, const int64_t* pos, int n_pos, int32_t* out, hipStream_t s);
+// resident.hip: a step's batch gathered out of a device-resident evaluation set in one launch (cpt_gather_batch)
+int gather_batch(const cpt_resident_store* st, const int32_t* seq_idx, int B, int Lt2, int Li2, int64_t* ids_o, int64_t* type_o, int64_t* mask_o,
+                 int64_t* mpos_o, float* img_o, hipStream_t s);
 
 }  // namespace cpt

@@ -18,6 +18,7 @@ import torch
 
 from . import batching
 from . import dist as cdist
+from . import resident as rsd
 from . import scoring
 from .train import get_lr_sched
 
@@ -38,6 +39,10 @@ logger = logging.getLogger(__name__)
 #   mask alone, both Q->AR blocks sharing one), and the host arrays and the grid are cut before the H2D copy: no device work, no synchronisation.
 #   The trimmed rows contribute exact zeros to the loss's gradient, so only the order of the sums changes; with dropout on, the masks are drawn
 #   for the shape that runs, so a trimmed step draws other masks than the padded one would (README "Length-aware training").
+#   Device-resident sets (resident.py; val_queries, val_rec and val_gqa take resident=None): with a ResidentSet the walk is computed up front
+#   from the set's host tables (bucket keys from text_len + regions, max_sequences from seq_first: no mask is scanned), the sequence indices of
+#   ALL steps go up in one copy per pass, and a step is resident.extent (trim) or the padded shape, ONE cpt_gather_batch, the unchanged forward
+#   and the unchanged choice launch.  No tensor of the items is read; the returns are the host path's, field for field and bit for bit.
 def _item_length(mask, Lt):
     """The length key of one item: text_len + regions of its longest sequence."""
     t, r = batching.extents(mask, Lt)
@@ -52,6 +57,26 @@ def _walk(n, size, keys=None, counts=None, cap=None):
     if cap is None:
         return [order[i:i + size] for i in range(0, n, size)]
     return [[order[i] for i in g] for g in batching.pack_queries([counts[i] for i in order], cap)]
+
+
+def _resident_walk(res, model, n_items, n_sequences, lo, hi, size, bucket, cap, trim, device, what):
+    """The walk of this rank's shard [lo, hi) over a ResidentSet: (groups as _walk gives them, {first item of a group: (its sequence indices
+    on the device, Lt', Li')}).  Everything comes from the set's host tables; the index lists of all groups go up in ONE copy."""
+    res.check_items(n_items, n_sequences, lo, hi, what)
+    res.check_model(model, what)
+    sf = res.seq_first
+    counts = (sf[lo + 1:hi + 1] - sf[lo:hi]).tolist() if cap is not None else None
+    groups = _walk(hi - lo, size, rsd.item_keys(res.tables) if bucket else None, counts, cap)
+    seqs = [np.concatenate([np.arange(sf[lo + i], sf[lo + i + 1]) for i in g]) for g in groups]
+    plans = {}
+    if seqs:
+        flat = rsd.h2d(np.concatenate(seqs).astype(np.int32), device, "seq_idx")
+        o = 0
+        for g, s in zip(groups, seqs):
+            lt, li = rsd.extent(res.tables, s) if trim else (res.Lt, res.Li)
+            plans[g[0]] = (flat[o:o + s.size], lt, li)
+            o += s.size
+    return groups, plans
 
 
 def _sel(idx, device, bucket):
@@ -108,7 +133,7 @@ def _trim_train_host(host, grid):
 
 
 def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4, colour_columns_only=True, trim=False, bucket=False,
-                max_sequences=None):
+                max_sequences=None, resident=None):
     """queries: list of dicts with tensors ``img_feats (P,Li,D)``, ``input_ids (P,Lt)``,
     ``segment_ids``, ``attention_mask (P,Lt+Li)``, ``mask_token_pos (P,)`` and python lists
     ``colors`` (per proposal sequence: colour-token ids) and ``rects`` (per sequence: rectangles).
@@ -116,8 +141,11 @@ def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4
     colour_columns_only (default): the decoder scores only the vocabulary columns the selection reads -- every colour id of the queries + ``none_id``
     (zeroshot/refcoco_cpt.py:219 gathers exactly those out of the (P, V) scores) -- instead of all V; same chosen indices.
     trim / bucket: length-aware evaluation, see the top of this module.  max_sequences: batches are consecutive groups of whole queries with at
-    most that many proposal sequences (batching.pack_queries) instead of ``batch_queries`` queries each -- even launches for ragged queries."""
+    most that many proposal sequences (batching.pack_queries) instead of ``batch_queries`` queries each -- even launches for ragged queries.
+    resident: a ResidentSet of these queries (resident.upload(resident.from_queries(queries), device)): the batches are gathered on the
+    device, only ``colors`` and ``rects`` of the queries are read; see the top of this module."""
     model.eval()
+    plans = {}
     col_ids, col_of, cols_dev = None, None, None
     if colour_columns_only:
         col_ids = sorted({int(c) for q in queries for s in q["colors"] for c in s} | {int(none_id)})
@@ -125,6 +153,11 @@ def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4
         cols_dev = torch.tensor(col_ids, dtype=torch.int64, device=device)
 
     def groups_of(lo, hi):
+        if resident is not None:
+            groups, found = _resident_walk(resident, model, len(queries), sum(len(q["colors"]) for q in queries), lo, hi, batch_queries, bucket,
+                                           max_sequences, trim, device, "val_queries")
+            plans.update(found)
+            return groups
         shard = queries[lo:hi]
         keys = [_item_length(q["attention_mask"], q["input_ids"].shape[1]) for q in shard] if bucket else None
         counts = [q["input_ids"].size(0) for q in shard] if max_sequences is not None else None
@@ -132,10 +165,13 @@ def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4
 
     def step(idx_local, lo):
         chunk = [queries[lo + i] for i in idx_local]
-        cat = {k: torch.cat([q[k] for q in chunk], 0) for k in ("img_feats", "input_ids", "segment_ids", "attention_mask", "mask_token_pos")}
-        if trim:
-            cat = _trim_host(cat, cat["mask_token_pos"])[0]
-        cat = {k: v.to(device, non_blocking=True) for k, v in cat.items()}
+        if resident is not None:
+            cat = resident.gather(*plans[idx_local[0]])
+        else:
+            cat = {k: torch.cat([q[k] for q in chunk], 0) for k in ("img_feats", "input_ids", "segment_ids", "attention_mask", "mask_token_pos")}
+            if trim:
+                cat = _trim_host(cat, cat["mask_token_pos"])[0]
+            cat = {k: v.to(device, non_blocking=True) for k, v in cat.items()}
         scores = model(cat["input_ids"], cat["segment_ids"], cat["attention_mask"], img_feats=cat["img_feats"],
                        mask_token_pos=cat["mask_token_pos"], vocab_columns=cols_dev)[0]      # (None: all V columns)
         # colour gather + per-query argmax run on the device (cpt_select_regions): only indices leave the GPU
@@ -144,7 +180,7 @@ def val_queries(model, queries, none_id, device, few_shot=False, batch_queries=4
             sets = [[col_of[int(c)] for c in s] for s in sets]
         first = [0]
         for q in chunk:
-            first.append(first[-1] + q["input_ids"].size(0))
+            first.append(first[-1] + (q["input_ids"].size(0) if resident is None else len(q["colors"])))   # (one colour list per sequence)
         return (scoring.select_regions_device(scores, sets, first, none_id if col_of is None else col_of[int(none_id)], few_shot=few_shot),)
 
     chosen, = _eval_pass(len(queries), groups_of, [((), torch.int64, -1)], step, device, bucket)
@@ -172,7 +208,7 @@ def _gather_ranges(buf, bounds):
 
 
 def val_rec(model, queries, gts, none_id, device, few_shot=False, batch_queries=4, colour_columns_only=True, trim=False, bucket=False,
-            max_sequences=None, table=None, return_candidate_scores=False):
+            max_sequences=None, table=None, return_candidate_scores=False, resident=None):
     """The whole of val() (zeroshot/refcoco_cpt.py:208-288, fewshot/refcoco_cpt.py:258-315) with the evaluation on the device: the pass of
     val_queries -- same queries, sharding, walking and trim / bucket / max_sequences -- whose step is concatenate, one forward, ONE launch
     (cpt_rec_choose): selection, the chosen box's float64 IoU against the annotation, correct = IoU > 0.5 and the counts, against tables
@@ -181,8 +217,10 @@ def val_rec(model, queries, gts, none_id, device, few_shot=False, batch_queries=
     Returns {"accuracy": percent = correct / evaluated, the number val() returns, "n_evaluated", "n_unpredicted" (queries without a colour),
     "predictions": {query index: (idx, rect)} as val_queries returns, "correct" (Q,) uint8, "iou" (Q,) float64, "score" (Q,) fp32 host arrays,
     and with return_candidate_scores "candidate_scores" (R_total,) fp32: every candidate's score, val()'s to_save_predictions[k]["scores"]
-    concatenated} on every rank.  A query without a colour or without an annotation is counted in neither sum."""
+    concatenated} on every rank.  A query without a colour or without an annotation is counted in neither sum.
+    resident: a ResidentSet of these queries, as val_queries takes it; the batches are then gathered on the device."""
     model.eval()
+    plans = {}
     if table is None:
         col_ids = sorted({int(c) for q in queries for s in q["colors"] for c in s} | {int(none_id)}) if colour_columns_only else None
         table = scoring.rec_eval_table(queries, gts, none_id, col_ids)
@@ -193,17 +231,25 @@ def val_rec(model, queries, gts, none_id, device, few_shot=False, batch_queries=
     out = scoring.rec_eval_buffers(table, device, return_candidate_scores)
 
     def groups_of(lo, hi):
+        if resident is not None:
+            groups, found = _resident_walk(resident, model, len(queries), int(table["seq_first"][-1]), lo, hi, batch_queries, bucket,
+                                           max_sequences, trim, device, "val_rec")
+            plans.update(found)
+            return groups
         shard = queries[lo:hi]
         keys = [_item_length(q["attention_mask"], q["input_ids"].shape[1]) for q in shard] if bucket else None
         counts = [q["input_ids"].size(0) for q in shard] if max_sequences is not None else None
         return _walk(hi - lo, batch_queries, keys, counts, max_sequences)
 
     def step(idx_local, lo):
-        cat = {k: torch.cat([queries[lo + i][k] for i in idx_local], 0)
-               for k in ("img_feats", "input_ids", "segment_ids", "attention_mask", "mask_token_pos")}
-        if trim:
-            cat = _trim_host(cat, cat["mask_token_pos"])[0]
-        cat = {k: v.to(device, non_blocking=True) for k, v in cat.items()}
+        if resident is not None:
+            cat = resident.gather(*plans[idx_local[0]])
+        else:
+            cat = {k: torch.cat([queries[lo + i][k] for i in idx_local], 0)
+                   for k in ("img_feats", "input_ids", "segment_ids", "attention_mask", "mask_token_pos")}
+            if trim:
+                cat = _trim_host(cat, cat["mask_token_pos"])[0]
+            cat = {k: v.to(device, non_blocking=True) for k, v in cat.items()}
         scores = model(cat["input_ids"], cat["segment_ids"], cat["attention_mask"], img_feats=cat["img_feats"],
                        mask_token_pos=cat["mask_token_pos"], vocab_columns=cols_dev)[0]
         scoring.rec_choose_device(scores, [lo + i for i in idx_local], table, few_shot, out)
@@ -486,15 +532,18 @@ def train_vcr_qar_batch(model, optimizer, scheduler, batches, opts, device, glob
 
 
 # ---- GQA-CPT (Oscar/oscar/fewshot/gqa_cpt.py; BASELINE config 4) and VCR Q->A (fewshot/vcr_nsp_cpt.py; config 5) -----------------------------
-def val_gqa(model, questions, labels, tokenizer, device, batch_questions=256, trim=False, bucket=False):
+def val_gqa(model, questions, labels, tokenizer, device, batch_questions=256, trim=False, bucket=False, resident=None):
     """Evaluation pass of gqa_cpt.py:558-636 (evaluate) on REC_MLM_CPT.  questions: prompts.assemble_gqa dicts with ``img_feats`` (Li, D) and
     ``igt``, the question's ground-truth label indices (eval_dic[str(q_id)]); labels: the data set's answer strings.  Questions are sharded over
     ranks; per batch ONE forward scores the label columns only (vocab_columns = every label's first word-piece id, duplicates kept) at the first
     [MASK] slot, and the argmax, the multi-ground-truth correctness and their count run in one launch (cpt_gqa_choose); the fixed-shape
     predictions, flags and (n, C) logits are gathered to every rank.  Accuracy as the reference: results de-duplicated by question_id (last
     wins), divided by the number of questions.  Returns {"preds" (n,) label columns, "answers" [the first-piece strings the reference reports],
-    "correct" (n,) uint8, "logits" (n, C), "q_ids", "acc"}.  trim / bucket: see the top of this module."""
+    "correct" (n,) uint8, "logits" (n, C), "q_ids", "acc"}.  trim / bucket: see the top of this module.
+    resident: a ResidentSet of these questions (resident.upload(resident.from_questions(questions), device)): the batches are gathered on the
+    device, only ``igt`` and ``q_id`` of the questions are read."""
     model.eval()
+    plans = {}
     token_ids, label_sid, piece_sid = scoring.gqa_string_ids(labels, tokenizer)
     _, answer_labels = scoring.gqa_first_pieces(labels, tokenizer)
     C = len(labels)
@@ -504,10 +553,21 @@ def val_gqa(model, questions, labels, tokenizer, device, batch_questions=256, tr
     t = lambda x: torch.as_tensor(x)
 
     def groups_of(lo, hi):
+        if resident is not None:
+            groups, found = _resident_walk(resident, model, len(questions), len(questions), lo, hi, batch_questions, bucket, None, trim, device,
+                                           "val_gqa")
+            plans.update(found)
+            return groups
         return _walk(hi - lo, batch_questions, [_item_length(np.asarray(q["input_mask"])[None], np.asarray(q["input_ids"]).shape[0])
                                                 for q in questions[lo:hi]] if bucket else None)
 
     def step(idx, lo):
+        if resident is not None:
+            b = resident.gather(*plans[idx[0]])
+            sc = model(b["input_ids"], b["segment_ids"], b["attention_mask"], img_feats=b["img_feats"], mask_token_pos=b["mask_token_pos"],
+                       vocab_columns=cols)[0]
+            p, c = scoring.gqa_choose_device(sc, piece, gt_all[torch.as_tensor(idx) + lo])
+            return p, c, sc
         chunk = [questions[lo + i] for i in idx]
         b = {"input_ids": torch.stack([t(q["input_ids"]) for q in chunk]), "segment_ids": torch.stack([t(q["segment_ids"]) for q in chunk]),
              "attention_mask": torch.stack([t(q["input_mask"]) for q in chunk]), "img_feats": torch.stack([t(q["img_feats"]) for q in chunk])}

@@ -344,6 +344,36 @@ int cpt_trim_batch_labels(const int64_t* input_ids, const int64_t* token_type, c
                           int64_t* label_grid_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Device-resident evaluation sets.  Added beside ABI 8; no existing struct changed.
+ * An evaluation split is uploaded ONCE as packed tables; every step's padded or trimmed batch is then built by one launch from a list of sequence
+ * indices, so that a pass uploads nothing but that list.  All pointers are device pointers.
+ * Sequences: n_seq sequences with the global indices [seq_base, seq_base + n_seq) (a data-parallel rank stores its shard only), padded Lt + Li:
+ *   ids [n_seq][Lt] int32, seg [n_seq][Lt] uint8, mask [n_seq][Lt + Li] uint8 (entries 0 / 1), mask_pos [n_seq] int32 (may be NULL when no call
+ *   asks for mask_pos_out), feat_block [n_seq] int32: the block that holds the sequence's region features.
+ * Blocks: block b holds block_rows[b] (0 .. Li) feature rows, the rows [block_off[b], block_off[b] + block_rows[b]) of feats; a region at or behind
+ *   block_rows reads as +0.0.  Sequences that share their features (the proposals of one image) name the same block.
+ * feats [n_rows][pitch] of feat_dtype CPT_F32 or CPT_BF16, img_dim <= pitch, the columns behind img_dim zero (cpt_pad_cast writes a chunk of
+ *   fp32 rows into exactly this form).  With feats 16-byte aligned, pitch a multiple of 16 bytes and img_dim even a lane moves 16 bytes per load
+ *   and per store; otherwise one element.  The three feature tables may be NULL when Li is 0.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    const void* feats;
+    const int32_t* ids; const uint8_t* seg; const uint8_t* mask; const int32_t* mask_pos; const int32_t* feat_block;
+    const int32_t* block_rows; const int64_t* block_off;
+    int64_t n_rows;
+    int32_t feat_dtype, pitch, img_dim, Lt, Li, n_seq, seq_base, n_blocks;
+} cpt_resident_store;
+/* One launch on `stream`: batch row b is sequence seq_idx[b] (seq_idx [B] int32 on the device: global indices, any order, repeats allowed).
+ * Writes what trimming the concatenated host batch gives (cpt_trim_batch): input_ids_out / token_type_out [B][Lt_out] int64 (text columns
+ * [0, Lt_out)), attn_mask_out [B][Lt_out + Li_out] int64 (text columns [0, Lt_out), then region columns [Lt, Lt + Li_out)), mask_pos_out [B] int64
+ * (or NULL), img_feats_out [B][Li_out][img_dim] fp32 (a bf16 store widened exactly; not touched when Li_out == 0).  1 <= Lt_out <= Lt,
+ * 0 <= Li_out <= Li.  EVERY element of every output is written, so the outputs need no initialisation.  The caller validates seq_idx; the kernel
+ * clamps an index outside the store (and a block index or block offset outside the tables) and never reads outside the store.
+ * CPT_ERR_SHAPE / CPT_ERR_NULL / CPT_ERR_ALIGN / CPT_ERR_DTYPE as cpt_trim_batch. */
+int cpt_gather_batch(const cpt_resident_store* store, const int32_t* seq_idx, int B, int Lt_out, int Li_out, int64_t* input_ids_out,
+                     int64_t* token_type_out, int64_t* attn_mask_out, int64_t* mask_pos_out, float* img_feats_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Few-shot training step (Oscar/oscar/fewshot/refcoco_cpt.py:231-249): forward that keeps the
  * activations, backward into caller-owned fp32 gradient tensors laid out like the parameters,
  * fused AdamW.  [MASK]-rows mode only (the loss of modeling_rec.py:147-150 sees only those rows).
