@@ -229,10 +229,11 @@ def nsp_cpt_scores(sd, cfg, input_ids, token_type_ids, attention_mask, img_feats
 
 
 def nsp_cpt_forward(sd, cfg, input_ids, token_type_ids, attention_mask, img_feats, next_sentence_label=None,
-                    w_key="cls.seq_relationship.weight", b_key="cls.seq_relationship.bias"):
+                    w_key="cls.seq_relationship.weight", b_key="cls.seq_relationship.bias", drop=None):
     """NSPCPT.forward (Oscar/oscar/modeling/modeling_vcr.py:115-129): relation scores on the pooled [CLS]
-    and, with labels, CrossEntropyLoss(ignore_index=-1) over the num_contrast_classes scores."""
-    _, pooled = bert_img_forward(sd, cfg, input_ids, token_type_ids, attention_mask, None, img_feats)
+    and, with labels, CrossEntropyLoss(ignore_index=-1) over the num_contrast_classes scores.  ``drop``: the dropout
+    multipliers of a training forward (``_drop``); None = eval mode."""
+    _, pooled = bert_img_forward(sd, cfg, input_ids, token_type_ids, attention_mask, None, img_feats, drop=drop)
     rel = relation_head(sd, pooled, w_key, b_key)
     if next_sentence_label is None:
         return (rel,)
@@ -376,6 +377,42 @@ def train_step_grads(sd, cfg, batch, names=None, drop=None, labels=None, bf16=Fa
             scores = scores[labels != -1]
         return loss.detach(), grads, scores.detach()
     return loss.detach(), grads
+
+
+def relation_loss(rel, labels):
+    """CrossEntropyLoss(ignore_index=-1) over a block's relation scores (modeling_vcr.py:124-127, :247-250): the mean over the labelled rows."""
+    return F.cross_entropy(rel.view(-1, rel.size(-1)), labels.view(-1), ignore_index=-1)
+
+
+def nsp_step_grads(sd, cfg, batch, labels, drop=None, bf16=False, B0=None, heads=(("cls.weight", "cls.bias"),)):
+    """loss.backward() of the NSP-CPT fine-tuning step (fewshot/vcr_nsp_cpt.py:425-470) and of the two-head VCR Q->AR step
+    (fewshot/vcr_qar_nsp_cpt.py:475-496), the counterpart of ``train_step_grads``: returns (loss, {name: grad}, rel).
+
+    ONE encoder pass over the whole batch (``drop``'s masks are indexed by row of the whole batch), then the relation head(s) on the
+    pooled [CLS].  ``heads``: the (weight key, bias key) of each head, named as the model under test names them -- one head
+    (``cls.*``, NSPCPT): CrossEntropyLoss(ignore_index=-1) over all rows of ``labels`` (B,); two heads (``cls_ans.*``, ``cls_rat.*``,
+    VCRQAR_NSPCPT): rows [0, B0) through head 0 and [B0, B) through head 1, the loss the SUM of the two blocks' means (q_a_loss +
+    qa_r_loss); an empty block (B0 = 0 or B: forward(head="rat" / "ans")) adds nothing.  ``rel``: the (B, n_rel) scores in row order.
+
+    Runs on the device and in the dtype of ``sd`` / ``batch``, under ``emulate_bf16(bf16)``.  A tensor of ``sd`` outside the loss's graph
+    (an MLM head, say) has gradient None."""
+    if len(heads) not in (1, 2) or (len(heads) == 2) != (B0 is not None):
+        raise ValueError("nsp_step_grads: one head and no B0, or two heads and B0")
+    leaves = {k: t.detach().clone().requires_grad_(True) for k, t in sd.items()}
+    with emulate_bf16(bf16):
+        _, pooled = bert_img_forward(leaves, cfg, batch["input_ids"], batch["segment_ids"], batch["attention_mask"], None,
+                                     batch["img_feats"], drop=drop)
+        B = pooled.size(0)
+        labels = labels.view(-1).to(pooled.device)
+        blocks = [(0, B)] if B0 is None else [(0, int(B0)), (int(B0), B)]
+        loss, rels = 0, []
+        for (lo, hi), (wk, bk) in zip(blocks, heads):
+            rel = relation_head(leaves, pooled[lo:hi], wk, bk)
+            rels.append(rel)
+            if hi > lo:
+                loss = loss + relation_loss(rel, labels[lo:hi])
+        loss.backward()
+    return loss.detach(), {k: t.grad for k, t in leaves.items()}, torch.cat(rels, 0).detach()
 
 
 # ---- dropout masks: CPU restatement of the counter scheme of cpt_amd/csrc/dropout.h (to pin the exported masks) --------

@@ -10,7 +10,8 @@ rel = ||got - ref|| / ||ref||, the whole tensor at once.
   8e-2 band the norm-only test allowed (OLD_BAND).  C is one constant for every parameter, shape and layer: a launch that drops,
   repeats or misplaces part of a sum leaves the emulation's rounding error behind by far more than C.  C = 2.5: over the Oscar-base sweep
   (1..53 sequences, 12 layers) the worst gradient ratio is 2.0 (a LayerNorm gain at 6240 rows), most tensors sit at 1.0..1.3; the loss,
-  whose emulation error is sometimes tiny by chance, is held by the floor.
+  whose emulation error is sometimes tiny by chance, is held by the floor.  Over the Oscar-large NSP-CPT / Q->AR sweep
+  (tests/test_gpu_train_large.py: hidden 1024, 2 layers, 265..4240 rows) the worst gradient ratio is 1.5 (layer 1's query bias at 2120 rows).
 * attention.self.key.bias: zero in exact arithmetic (softmax is shift-invariant), both sides hold rounding noise -> an absolute bound.
 
 ``check`` raises with a per-layer table (the worst parameter of layers 11 -> 0, then the embeddings and the head), so that error growth
@@ -34,11 +35,12 @@ def rel(got, ref):
 
 
 def group(name):
-    """'layer N', 'embeddings' (text and region embeddings, their LayerNorms) or 'head' (transform, decoder bias, loss, scores)."""
+    """'layer N', 'embeddings' (text and region embeddings, their LayerNorms) or 'head' (transform, decoder bias, the pooler and the
+    relation heads, loss, scores)."""
     m = _LAYER.match(name)
     if m:
         return "layer %d" % int(m.group(1))
-    if name.startswith("bert."):
+    if name.startswith("bert.") and not name.startswith("bert.pooler."):
         return "embeddings"
     return "head"
 
