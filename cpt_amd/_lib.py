@@ -89,6 +89,11 @@ class ResidentStore(C.Structure):
                [("n_rows", C.c_int64)] + [(n, C.c_int32) for n in ("feat_dtype", "pitch", "img_dim", "Lt", "Li", "n_seq", "seq_base", "n_blocks")]
 
 
+class ResidentHeads(C.Structure):
+    """cpt_resident_heads: the head rows, their labels and the sequence labels of a resident set (cpt_amd/resident.py)."""
+    _fields_ = [(n, C.c_void_p) for n in ("head_first", "head_pos", "head_label", "seq_label")] + [("n_heads", C.c_int32)]
+
+
 _SIGS = {
     "cpt_version": (C.c_int, []),
     "cpt_last_error": (C.c_char_p, []),
@@ -112,6 +117,8 @@ _SIGS = {
     "cpt_train_extents": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp]),
     "cpt_trim_batch_labels": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]),
     "cpt_gather_batch": (C.c_int, [C.POINTER(ResidentStore), vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "cpt_gather_batch_heads": (C.c_int, [C.POINTER(ResidentStore), C.POINTER(ResidentHeads), vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp,
+                                         vp, vp, vp, vp, vp]),
     "cpt_train_fwd_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(Batch), C.POINTER(Outputs), vp, C.c_size_t, vp, BUCKET_CB, vp,
                                      C.POINTER(Dropout)]),
     "cpt_train_bwd_rel2": (C.c_int, [C.POINTER(Model), C.POINTER(Rel2), C.POINTER(Batch), C.POINTER(ModelGrads), C.c_float, vp, vp, C.c_size_t, vp,

@@ -1182,4 +1182,23 @@ int cpt_gather_batch(const cpt_resident_store* store, const int32_t* seq_idx, in
                                        (hipStream_t)stream), "cpt_gather_batch");
 }
 
+int cpt_gather_batch_heads(const cpt_resident_store* store, const cpt_resident_heads* heads, const int32_t* seq_idx, const int32_t* row_first, int B, int R,
+                           int Lt_out, int Li_out, int64_t* input_ids_out, int64_t* token_type_out, int64_t* attn_mask_out, int64_t* mask_pos_out,
+                           float* img_feats_out, int64_t* head_rows_out, int64_t* head_labels_out, int64_t* label_grid_out, int64_t* seq_label_out,
+                           void* stream) {
+    if (!store || !heads || !seq_idx || !input_ids_out || !token_type_out || !attn_mask_out || (Li_out > 0 && !img_feats_out))
+        return abi_fail(CPT_ERR_NULL, "cpt_gather_batch_heads: null argument");
+    if (B <= 0 || R < 0 || Lt_out <= 0 || Lt_out > store->Lt || Li_out < 0 || Li_out > store->Li || store->n_seq <= 0 ||
+        (Li_out > 0 && store->img_dim <= 0) || heads->n_heads < 0)
+        return abi_fail(CPT_ERR_SHAPE, "cpt_gather_batch_heads: B %d, R %d, %d + %d -> %d + %d, img_dim %d, %d sequences, %d head entries", B, R, store->Lt,
+                        store->Li, Lt_out, Li_out, store->img_dim, store->n_seq, heads->n_heads);
+    if (((head_labels_out && R > 0) || label_grid_out) && !heads->head_label)
+        return abi_fail(CPT_ERR_NULL, "cpt_gather_batch_heads: labels asked for of a set without head_label");
+    if (seq_label_out && !heads->seq_label)
+        return abi_fail(CPT_ERR_NULL, "cpt_gather_batch_heads: sequence labels asked for of a set without seq_label");
+    return abi_check(cpt::gather_batch_heads(store, heads, seq_idx, row_first, B, R, Lt_out, Li_out, input_ids_out, token_type_out, attn_mask_out,
+                                             mask_pos_out, img_feats_out, head_rows_out, head_labels_out, label_grid_out, seq_label_out,
+                                             (hipStream_t)stream), "cpt_gather_batch_heads");
+}
+
 }  // extern "C"

@@ -329,5 +329,9 @@ int train_extents(const int64_t* mask, int B, int Lt, int Li, const int64_t* gri
 // resident.hip: a step's batch gathered out of a device-resident evaluation set in one launch (cpt_gather_batch)
 int gather_batch(const cpt_resident_store* st, const int32_t* seq_idx, int B, int Lt2, int Li2, int64_t* ids_o, int64_t* type_o, int64_t* mask_o,
                  int64_t* mpos_o, float* img_o, hipStream_t s);
+// resident.hip: the same launch with the head rows, their labels, the label grid and the sequence labels (cpt_gather_batch_heads)
+int gather_batch_heads(const cpt_resident_store* st, const cpt_resident_heads* hd, const int32_t* seq_idx, const int32_t* row_first, int B, int R,
+                       int Lt2, int Li2, int64_t* ids_o, int64_t* type_o, int64_t* mask_o, int64_t* mpos_o, float* img_o, int64_t* rows_o,
+                       int64_t* hlab_o, int64_t* grid_o, int64_t* slab_o, hipStream_t s);
 
 }  // namespace cpt

@@ -173,15 +173,108 @@ __global__ __launch_bounds__(GB_THREADS) void gather_batch_kernel(GatherArgs a) 
     } else gather_rows_block(a, blockIdx.x - a.nfeat, gridDim.x - a.nfeat);
 }
 
-int gather_batch(const cpt_resident_store* st, const int32_t* seq_idx, int B, int Lt2, int Li2, int64_t* ids_o, int64_t* type_o, int64_t* mask_o,
-                 int64_t* mpos_o, float* img_o, hipStream_t s) {
+// ---- cpt_gather_batch_heads: the same launch with the head rows, the labels and the label grid ------------------------------------------------
+// A set with head tables (cpt_resident_heads) names, per sequence, the positions a head reads ([MASK] rows) and their labels.  The feature
+// workgroups are those of gather_batch_kernel.  The int64-row workgroups write, beside the rows above:
+//   label grid  (B, Lt' + Li') of -1 with head_label at the row's head positions, by the workgroups that write the mask row and with the mask's index
+//               arithmetic (text column c is padded column c, region column Lt' + j is padded column Lt + j); per element the sequence's few head
+//               entries are walked, so that every element is written exactly once: no atomics, no fill in front.
+//   head rows   row_first[b] + k = (b, position) of the k-th head entry of sequence seq_idx[b], with its label; one lane per row, the batch entry
+//               found by bisection of row_first ([B + 1], the exclusive prefix sum of the head counts of the batch, built by the host).
+//   sequence labels  one per batch entry (the relation heads).
+// Every index read from memory is clamped: head_first into [0, n_heads], a position into [0, Lt + Li), row_first into [0, R].
+struct GatherHeadArgs {
+    GatherArgs g;
+    const int32_t *head_first, *head_pos, *head_label, *seq_label, *row_first;
+    int n_heads, R;
+    int64_t *rows_o, *hlab_o, *grid_o, *slab_o;
+};
+
+__device__ __forceinline__ int clamp_i(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// the head entries [h0, h1) of store-local sequence `seq`, inside [0, n_heads]
+__device__ __forceinline__ void head_range(const GatherHeadArgs& a, int seq, int& h0, int& h1) {
+    h0 = clamp_i(a.head_first[seq], 0, a.n_heads);
+    h1 = clamp_i(a.head_first[seq + 1], h0, a.n_heads);
+}
+
+__device__ __forceinline__ void gather_rows_heads_block(const GatherHeadArgs& a, unsigned block, unsigned nblocks) {
+    const GatherArgs& g = a.g;
+    const unsigned L = g.Lt + g.Li, L2 = g.Lt2 + g.Li2;
+    const size_t n_text = (size_t)g.B * g.Lt2, n_mask = (size_t)g.B * L2, n_pos = g.mpos_o ? (size_t)g.B : 0, n_slab = a.slab_o ? (size_t)g.B : 0;
+    const size_t n_rows = (a.rows_o || a.hlab_o) ? (size_t)a.R : 0, n = n_text + n_mask + n_pos + n_slab + n_rows;
+    const size_t stride = (size_t)nblocks * GB_THREADS;
+    for (size_t idx = (size_t)block * GB_THREADS + threadIdx.x; idx < n; idx += stride) {
+        if (idx < n_text) {
+            const unsigned b = (unsigned)(idx / g.Lt2), t = (unsigned)(idx % g.Lt2);
+            const size_t src = (size_t)gather_seq(g, b) * g.Lt + t;
+            g.ids_o[idx] = g.ids[src];
+            g.type_o[idx] = g.seg[src];
+        } else if (idx < n_text + n_mask) {
+            const size_t j = idx - n_text;
+            const unsigned b = (unsigned)(j / L2), c = (unsigned)(j % L2);
+            const int seq = gather_seq(g, b);
+            const unsigned pc = c < (unsigned)g.Lt2 ? c : g.Lt + (c - g.Lt2);          // the padded column of output column c
+            g.mask_o[j] = g.mask[(size_t)seq * L + pc];
+            if (a.grid_o) {
+                int h0, h1;
+                head_range(a, seq, h0, h1);
+                long long lab = -1;
+                for (int h = h0; h < h1; ++h)
+                    if ((unsigned)a.head_pos[h] == pc) lab = a.head_label[h];
+                a.grid_o[j] = lab;
+            }
+        } else if (idx < n_text + n_mask + n_pos) {
+            const unsigned b = (unsigned)(idx - n_text - n_mask);
+            g.mpos_o[b] = g.mask_pos[gather_seq(g, b)];
+        } else if (idx < n_text + n_mask + n_pos + n_slab) {
+            const unsigned b = (unsigned)(idx - n_text - n_mask - n_pos);
+            a.slab_o[b] = a.seq_label[gather_seq(g, b)];
+        } else {
+            const int r = (int)(idx - n_text - n_mask - n_pos - n_slab);
+            int lo = 0, hi = g.B - 1;                                                  // the last batch entry whose first row is <= r
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (clamp_i(a.row_first[mid], 0, a.R) <= r) lo = mid;
+                else hi = mid - 1;
+            }
+            int h0, h1;
+            head_range(a, gather_seq(g, (unsigned)lo), h0, h1);
+            const int k = r - clamp_i(a.row_first[lo], 0, a.R);
+            long long pos = 0, lab = -1;                                               // (a sequence without an entry: tables that disagree)
+            if (h1 > h0) {
+                const int h = h0 + clamp_i(k, 0, h1 - h0 - 1);
+                pos = clamp_i(a.head_pos[h], 0, (int)L - 1);
+                if (a.hlab_o) lab = a.head_label[h];
+            }
+            if (a.rows_o) {
+                a.rows_o[2 * (size_t)r] = lo;
+                a.rows_o[2 * (size_t)r + 1] = pos;
+            }
+            if (a.hlab_o) a.hlab_o[r] = lab;
+        }
+    }
+}
+
+template <typename T, bool VEC>
+__global__ __launch_bounds__(GB_THREADS) void gather_batch_heads_kernel(GatherHeadArgs a) {
+    if (blockIdx.x < a.g.nfeat) {
+        if constexpr (VEC) gather_feats_vec<T>(a.g, blockIdx.x);
+        else gather_feats_scalar<T>(a.g, blockIdx.x);
+    } else gather_rows_heads_block(a, blockIdx.x - a.g.nfeat, gridDim.x - a.g.nfeat);
+}
+
+// the checks of a launch, its feature form and its grid: shared by gather_batch and gather_batch_heads (extra: int64 elements beside the rows
+// of gather_batch)
+static int gather_plan(const cpt_resident_store* st, const int32_t* seq_idx, int B, int Lt2, int Li2, int64_t* ids_o, int64_t* type_o, int64_t* mask_o,
+                       int64_t* mpos_o, float* img_o, size_t extra, GatherArgs& a, bool& vec, size_t& nrow) {
     if (!st || !seq_idx || !ids_o || !type_o || !mask_o) return CPT_ERR_NULL;
     const int Lt = st->Lt, Li = st->Li, D = st->img_dim;
     if (B <= 0 || Lt <= 0 || Li < 0 || Lt2 <= 0 || Lt2 > Lt || Li2 < 0 || Li2 > Li || st->n_seq <= 0) return CPT_ERR_SHAPE;
     if (!st->ids || !st->seg || !st->mask || (mpos_o && !st->mask_pos)) return CPT_ERR_NULL;
     if (st->feat_dtype != CPT_F32 && st->feat_dtype != CPT_BF16) return CPT_ERR_DTYPE;
     const size_t esz = st->feat_dtype == CPT_BF16 ? 2 : 4;
-    bool vec = false;
+    vec = false;
     size_t nfeat = 0;
     if (Li2 > 0) {
         if (D <= 0 || st->pitch < D || st->n_blocks <= 0 || st->n_rows < 0) return CPT_ERR_SHAPE;
@@ -196,18 +289,59 @@ int gather_batch(const cpt_resident_store* st, const int32_t* seq_idx, int B, in
         nfeat = (work + (size_t)GB_THREADS * GB_UNR - 1) / ((size_t)GB_THREADS * GB_UNR);
         if (!vec && nfeat > 4096) nfeat = 4096;
     }
-    const size_t rows = (size_t)B * Lt2 + (size_t)B * (Lt2 + Li2) + (size_t)B;
-    size_t nrow = (rows + (size_t)GB_THREADS * 4 - 1) / ((size_t)GB_THREADS * 4);
+    const size_t rows = (size_t)B * Lt2 + (size_t)B * (Lt2 + Li2) + (size_t)B + extra;
+    nrow = (rows + (size_t)GB_THREADS * 4 - 1) / ((size_t)GB_THREADS * 4);
     nrow = nrow < 1 ? 1 : (nrow > 1024 ? 1024 : nrow);
-    GatherArgs a{st->feats, st->ids, st->seg, st->mask, st->mask_pos, st->feat_block, st->block_rows, st->block_off, (long long)st->n_rows,
-                 st->pitch, D, Lt, Li, st->n_seq, st->seq_base, st->n_blocks, seq_idx, B, Lt2, Li2, ids_o, type_o, mask_o, mpos_o, img_o, (unsigned)nfeat};
-    const dim3 grid((unsigned)(nfeat + nrow)), block(GB_THREADS);
+    a = GatherArgs{st->feats, st->ids, st->seg, st->mask, st->mask_pos, st->feat_block, st->block_rows, st->block_off, (long long)st->n_rows,
+                   st->pitch, D, Lt, Li, st->n_seq, st->seq_base, st->n_blocks, seq_idx, B, Lt2, Li2, ids_o, type_o, mask_o, mpos_o, img_o, (unsigned)nfeat};
+    return CPT_OK;
+}
+
+int gather_batch(const cpt_resident_store* st, const int32_t* seq_idx, int B, int Lt2, int Li2, int64_t* ids_o, int64_t* type_o, int64_t* mask_o,
+                 int64_t* mpos_o, float* img_o, hipStream_t s) {
+    GatherArgs a;
+    bool vec;
+    size_t nrow;
+    const int rc = gather_plan(st, seq_idx, B, Lt2, Li2, ids_o, type_o, mask_o, mpos_o, img_o, 0, a, vec, nrow);
+    if (rc != CPT_OK) return rc;
+    const dim3 grid((unsigned)(a.nfeat + nrow)), block(GB_THREADS);
     if (st->feat_dtype == CPT_BF16) {
         if (vec) gather_batch_kernel<bf16, true><<<grid, block, 0, s>>>(a);
         else gather_batch_kernel<bf16, false><<<grid, block, 0, s>>>(a);
     } else {
         if (vec) gather_batch_kernel<float, true><<<grid, block, 0, s>>>(a);
         else gather_batch_kernel<float, false><<<grid, block, 0, s>>>(a);
+    }
+    return CPT_OK;
+}
+
+int gather_batch_heads(const cpt_resident_store* st, const cpt_resident_heads* hd, const int32_t* seq_idx, const int32_t* row_first, int B, int R,
+                       int Lt2, int Li2, int64_t* ids_o, int64_t* type_o, int64_t* mask_o, int64_t* mpos_o, float* img_o, int64_t* rows_o,
+                       int64_t* hlab_o, int64_t* grid_o, int64_t* slab_o, hipStream_t s) {
+    if (!hd) return CPT_ERR_NULL;
+    if (R < 0 || hd->n_heads < 0) return CPT_ERR_SHAPE;
+    const bool rows = (rows_o || hlab_o) && R > 0;                     // (R = 0: the row outputs are empty, nothing of theirs is read)
+    if ((rows || grid_o) && (!hd->head_first || (hd->n_heads > 0 && !hd->head_pos))) return CPT_ERR_NULL;
+    if (rows && !row_first) return CPT_ERR_NULL;
+    if (((hlab_o && R > 0) || grid_o) && !hd->head_label) return CPT_ERR_NULL;
+    if (slab_o && !hd->seq_label) return CPT_ERR_NULL;
+    if (rows && hd->n_heads == 0) return CPT_ERR_SHAPE;                // (rows to write and no entry to take them from)
+    GatherHeadArgs a;
+    bool vec;
+    size_t nrow;
+    const size_t extra = (slab_o ? (size_t)B : 0) + (rows ? (size_t)R : 0) + (grid_o && st ? (size_t)B * (size_t)(Lt2 + Li2 > 0 ? Lt2 + Li2 : 0) : 0);
+    const int rc = gather_plan(st, seq_idx, B, Lt2, Li2, ids_o, type_o, mask_o, mpos_o, img_o, extra, a.g, vec, nrow);
+    if (rc != CPT_OK) return rc;
+    a.head_first = hd->head_first, a.head_pos = hd->head_pos, a.head_label = hd->head_label, a.seq_label = hd->seq_label, a.row_first = row_first;
+    a.n_heads = hd->n_heads, a.R = rows ? R : 0;
+    a.rows_o = rows ? rows_o : nullptr, a.hlab_o = rows ? hlab_o : nullptr, a.grid_o = grid_o, a.slab_o = slab_o;
+    const dim3 grid((unsigned)(a.g.nfeat + nrow)), block(GB_THREADS);
+    if (st->feat_dtype == CPT_BF16) {
+        if (vec) gather_batch_heads_kernel<bf16, true><<<grid, block, 0, s>>>(a);
+        else gather_batch_heads_kernel<bf16, false><<<grid, block, 0, s>>>(a);
+    } else {
+        if (vec) gather_batch_heads_kernel<float, true><<<grid, block, 0, s>>>(a);
+        else gather_batch_heads_kernel<float, false><<<grid, block, 0, s>>>(a);
     }
     return CPT_OK;
 }

@@ -43,6 +43,12 @@ logger = logging.getLogger(__name__)
 #   from the set's host tables (bucket keys from text_len + regions, max_sequences from seq_first: no mask is scanned), the sequence indices of
 #   ALL steps go up in one copy per pass, and a step is resident.extent (trim) or the padded shape, ONE cpt_gather_batch, the unchanged forward
 #   and the unchanged choice launch.  No tensor of the items is read; the returns are the host path's, field for field and bit for bit.
+#   val_vg, val_vcr and val_vcr_qar take resident= too (sets with head tables: resident.from_pairs / from_vcr / from_vcr_qar).  VG sequences hold
+#   1, 2 or 3 [MASK] rows, so a VG step is ONE cpt_gather_batch_heads, which also writes the (n, 2) head rows; their prefix sums (row_first) go up
+#   with the index lists, still one copy per pass.  A Q->AR step gathers both blocks in one launch (all Q->A sequences, then all QA->R).
+#   Training: train_batch, train_vg_batch and tune_soft_template take resident= (resident.from_train_batches); ``batches`` is then an iterable of
+#   1-D arrays of global sequence indices -- any grouping, so an epoch's reshuffle costs an index list -- and a step's batch AND its label grid
+#   come from one cpt_gather_batch_heads (trim=True: cut to resident.extent of that batch, the rule of batching.label_extent).
 def _item_length(mask, Lt):
     """The length key of one item: text_len + regions of its longest sequence."""
     t, r = batching.extents(mask, Lt)
@@ -59,23 +65,38 @@ def _walk(n, size, keys=None, counts=None, cap=None):
     return [[order[i] for i in g] for g in batching.pack_queries([counts[i] for i in order], cap)]
 
 
-def _resident_walk(res, model, n_items, n_sequences, lo, hi, size, bucket, cap, trim, device, what):
+def _upload_lists(lists, device):
+    """int32 lists -> their device tensors, slices of ONE copy."""
+    flat = rsd.h2d(np.concatenate(lists).astype(np.int32), device, "seq_idx")
+    out, o = [], 0
+    for x in lists:
+        out.append(flat[o:o + x.size])
+        o += x.size
+    return out
+
+
+def _resident_walk(res, model, n_items, n_sequences, lo, hi, size, bucket, cap, trim, device, what, heads=False, order=None):
     """The walk of this rank's shard [lo, hi) over a ResidentSet: (groups as _walk gives them, {first item of a group: (its sequence indices
-    on the device, Lt', Li')}).  Everything comes from the set's host tables; the index lists of all groups go up in ONE copy."""
+    on the device, Lt', Li')}).  Everything comes from the set's host tables; the index lists of all groups go up in ONE copy.
+    heads: a plan is (sequence indices, Lt', Li', row_first on the device, R) -- the prefix sums of the head counts of every group ride in the
+    same copy.  order(group) -> the group's sequence indices, where they are not the items' sequences one item after the other (Q->AR)."""
     res.check_items(n_items, n_sequences, lo, hi, what)
     res.check_model(model, what)
     sf = res.seq_first
     counts = (sf[lo + 1:hi + 1] - sf[lo:hi]).tolist() if cap is not None else None
     groups = _walk(hi - lo, size, rsd.item_keys(res.tables) if bucket else None, counts, cap)
-    seqs = [np.concatenate([np.arange(sf[lo + i], sf[lo + i + 1]) for i in g]) for g in groups]
+    if heads and not rsd.has_heads(res.tables):
+        raise ValueError("%s: the resident set has no head tables (it was built for another driver)" % what)
+    if order is None:
+        order = lambda g: np.concatenate([np.arange(sf[lo + i], sf[lo + i + 1]) for i in g])
+    seqs = [order(g) for g in groups]
     plans = {}
     if seqs:
-        flat = rsd.h2d(np.concatenate(seqs).astype(np.int32), device, "seq_idx")
-        o = 0
-        for g, s in zip(groups, seqs):
+        firsts = [rsd.row_first(res.tables, s) for s in seqs] if heads else []
+        dev = _upload_lists(seqs + firsts, device)
+        for k, (g, s) in enumerate(zip(groups, seqs)):
             lt, li = rsd.extent(res.tables, s) if trim else (res.Lt, res.Li)
-            plans[g[0]] = (flat[o:o + s.size], lt, li)
-            o += s.size
+            plans[g[0]] = (dev[k], lt, li) + ((dev[len(seqs) + k], int(firsts[k][-1])) if heads else ())
     return groups, plans
 
 
@@ -315,14 +336,46 @@ def _device_batch(host_batch, grid_fn, device, trim):
     return batch, grid.to(device)
 
 
-def _scheduled_pass(model, optimizer, batches, opts, device, global_step, grid_fn, trim=False):
+def _resident_batches(res, model, batches, device, trim, what):
+    """The training steps of a pass over a ResidentSet (resident.from_train_batches): ``batches`` is an iterable of 1-D integer arrays of global
+    sequence indices.  The lists are materialised once and go up in ONE copy; yields per step (batch, label grid), both written by one
+    cpt_gather_batch_heads.  trim: every batch is cut to resident.extent of its sequences (labelled positions kept)."""
+    if res._store is None:
+        raise RuntimeError("%s: the resident set was freed" % what)
+    t = res.tables
+    if not rsd.has_heads(t) or t["head_label"] is None:
+        raise ValueError("%s: the resident set has no labelled head rows (build it with resident.from_train_batches)" % what)
+    res.check_model(model, what)
+    lists = []
+    for b in batches:
+        b = np.asarray(b.cpu() if hasattr(b, "cpu") else b)
+        if b.ndim != 1 or b.dtype.kind not in "iu" or b.size == 0:
+            raise ValueError("%s: with a resident set a batch is a non-empty 1-D integer array of sequence indices, got %s %s" % (what, b.dtype, b.shape))
+        rsd._local(t, b)                                   # (raises for an index outside the stored sequences)
+        lists.append(b.astype(np.int64))
+    dev = _upload_lists(lists, device) if lists else []
+
+    def steps():
+        for seq, idx in zip(dev, lists):
+            lt, li = rsd.extent(t, idx, labelled=True) if trim else (res.Lt, res.Li)
+            b = res.gather(seq, lt, li, mask_pos=False, heads=("label_grid",))
+            if li == 0:
+                b["img_feats"] = None                      # Li' = 0: the step runs text-only, as it does without regions
+            yield b, b["label_grid"]
+    return steps()
+
+
+def _scheduled_pass(model, optimizer, batches, opts, device, global_step, grid_fn, trim=False, resident=None, what="train_batch"):
     """The loop train_batch and train_vg_batch share: per batch the scheduled learning rate, then zero_grad / forward with
     masked_lm_labels=grid_fn(batch) / backward / step; a step that raises RuntimeError is logged and skipped without advancing the schedule.
-    Returns (global_step, [loss tensors])."""
+    Returns (global_step, [loss tensors]).  resident: the batches and their grids are gathered on the device (_resident_batches)."""
     model.train()
     losses = []
-    for index, host_batch in enumerate(batches):
-        batch, grid = _device_batch(host_batch, grid_fn, device, trim)
+    if resident is not None:
+        steps = _resident_batches(resident, model, batches, device, trim, what)
+    else:
+        steps = (_device_batch(host_batch, grid_fn, device, trim) for host_batch in batches)
+    for index, (batch, grid) in enumerate(steps):
         _apply_lr(optimizer, get_lr_sched(global_step, opts), getattr(opts, "lr_mul", 1.0))
         try:
             optimizer.zero_grad()
@@ -338,25 +391,31 @@ def _scheduled_pass(model, optimizer, batches, opts, device, global_step, grid_f
     return global_step, losses
 
 
-def train_batch(model, optimizer, batches, opts, device, global_step=0, trim=False):
+def train_batch(model, optimizer, batches, opts, device, global_step=0, trim=False, resident=None):
     """One pass over ``batches`` (dicts with img_feats, input_ids, attention_mask, segment_ids, mask_token_pos, colors): the few-shot
     step of fewshot/refcoco_cpt.py:225-255 -- label grid, scheduled learning rate, zero_grad / forward / backward / step; a step that
     raises RuntimeError is logged and skipped without advancing the schedule (_scheduled_pass).  Returns (global_step, [loss tensors]).
-    trim: length-aware training, see the top of this module."""
-    return _scheduled_pass(model, optimizer, batches, opts, device, global_step, _label_grid, trim)
+    trim: length-aware training, see the top of this module.
+    resident: a ResidentSet of the training batches (resident.upload(resident.from_train_batches(batch dicts), device)); ``batches`` is then an
+    iterable of 1-D integer arrays of global sequence indices into it (resident.batch_indices(): the grouping it was built from; any other
+    grouping is allowed) and every step's batch and label grid are gathered on the device by one launch."""
+    return _scheduled_pass(model, optimizer, batches, opts, device, global_step, _label_grid, trim, resident, "train_batch")
 
 
-def tune_soft_template(model, optimizer, batches, device, trim=False):
+def tune_soft_template(model, optimizer, batches, device, trim=False, resident=None):
     """The template-tuning loop of explore/sgd_to_explore_template.py:396-412 on a model with a soft template attached
     (cpt_amd/soft_prompt.py attach; ``optimizer`` is any torch optimizer over that one tensor -- the reference builds
     ``AdamW([template], lr=0.02, eps=1e-8)``): per batch the label grid with the colour id at the [MASK] position, the loss divided
     ADDITIONALLY by the batch size (:409), zero_grad / backward / step.  Returns the list of (divided) loss tensors.
     The reference runs this loop on BertImgForPreTraining with next_sentence_label=0, so its loss also carries the contrastive term;
-    here it is REC_MLM_CPT's MLM loss alone.  trim: length-aware training, see the top of this module."""
+    here it is REC_MLM_CPT's MLM loss alone.  trim: length-aware training, see the top of this module.  resident: as train_batch takes it."""
     model.train()
     losses = []
-    for host_batch in batches:
-        batch, grid = _device_batch(host_batch, _label_grid, device, trim)
+    if resident is not None:
+        steps = _resident_batches(resident, model, batches, device, trim, "tune_soft_template")
+    else:
+        steps = (_device_batch(host_batch, _label_grid, device, trim) for host_batch in batches)
+    for batch, grid in steps:
         optimizer.zero_grad()
         loss = model(batch["input_ids"], batch["segment_ids"], batch["attention_mask"], img_feats=batch["img_feats"],
                      masked_lm_labels=grid)[0]
@@ -384,22 +443,35 @@ def _vg_cat(chunk, device, per_pair, trim=False):
     return out
 
 
-def val_vg(model, pairs, idx2pred, device, batch_pairs=16, trim=False, bucket=False):
+def val_vg(model, pairs, idx2pred, device, batch_pairs=16, trim=False, bucket=False, resident=None):
     """Zero-shot / evaluation pass of vg_cpt.py:255-305.  pairs: one dict per TSV row -- ``img_key`` (the image name), ``input_ids``
     (6, Lt), ``segment_ids``, ``attention_mask`` (6, Lt + Li), ``mask_token_pos`` (12, 2) as prompts.assemble_vg_zsl gives them, and
     ``img_feats`` (Li, D) or (6, Li, D).  Pairs are sharded across ranks as val_queries shards queries; each batch is scored on the
     device (scoring.vg_predicate_scores) and the fixed-shape (pairs, 2, C) scores are gathered with one all_gather.
     Returns (scores (pairs, 2, C) fp32 on the device, keys): keys[2 i] = pair i's key, keys[2 i + 1] = its reverse_imkey -- the rows of
-    scores.view(-1, C), in dataset order, as scoring.vg_eval_table takes them.  trim / bucket: see the top of this module."""
+    scores.view(-1, C), in dataset order, as scoring.vg_eval_table takes them.  trim / bucket: see the top of this module.
+    resident: a ResidentSet of these pairs (resident.upload(resident.from_pairs(pairs), device)): every batch and its head rows are gathered on
+    the device by one launch, only ``img_key`` of the pairs is read."""
     model.eval()
     C = max(int(i) for i in idx2pred) + 1
+    plans = {}
 
     def groups_of(lo, hi):
+        if resident is not None:
+            groups, found = _resident_walk(resident, model, len(pairs), 6 * len(pairs), lo, hi, batch_pairs, bucket, None, trim, device, "val_vg",
+                                           heads=True)
+            plans.update(found)
+            return groups
         return _walk(hi - lo, batch_pairs,
                      [_item_length(q["attention_mask"], np.asarray(q["input_ids"]).shape[1]) for q in pairs[lo:hi]] if bucket else None)
 
     def step(idx, lo):
-        b = _vg_cat([pairs[lo + i] for i in idx], device, 6, trim)
+        if resident is not None:
+            seq, lt, li, first, R = plans[idx[0]]
+            b = resident.gather(seq, lt, li, mask_pos=False, row_first=first, R=R, heads=("head_rows",))
+            b["mask_token_pos"] = b["head_rows"]
+        else:
+            b = _vg_cat([pairs[lo + i] for i in idx], device, 6, trim)
         return (scoring.vg_predicate_scores(model, b["input_ids"], b["segment_ids"], b["attention_mask"], b["img_feats"], b["mask_token_pos"],
                                             idx2pred),)
 
@@ -426,13 +498,14 @@ def vg_schedule(opts, num_train_epochs):
     return opts
 
 
-def train_vg_batch(model, optimizer, batches, opts, device, global_step=0, trim=False):
+def train_vg_batch(model, optimizer, batches, opts, device, global_step=0, trim=False, resident=None):
     """One pass of vg_cpt.py:217-252 (train_batch) over ``batches``: dicts with img_feats, input_ids, attention_mask, segment_ids,
     mask_token_pos (n, 2) (sequence, position) and row_labels (n,) -- prompts.assemble_vg_train rows concatenated, 6 labelled rows per
     pair.  The label grid holds several labelled positions per sequence (the multi-row training path of REC_MLM_CPT.forward); LR
     schedule (opts from vg_schedule), zero_grad / forward / backward / step and the skipped-step rule as train_batch (_scheduled_pass).
-    Returns (global_step, [loss tensors]).  trim: length-aware training, see the top of this module."""
-    return _scheduled_pass(model, optimizer, batches, opts, device, global_step, vg_label_grid, trim)
+    Returns (global_step, [loss tensors]).  trim: length-aware training, see the top of this module.  resident: as train_batch takes it (the
+    set built from these batch dicts: every sequence owns its labelled rows)."""
+    return _scheduled_pass(model, optimizer, batches, opts, device, global_step, vg_label_grid, trim, resident, "train_vg_batch")
 
 
 # ---- VCR Q->AR (Oscar/oscar/fewshot/vcr_qar_nsp_cpt.py; launched by cmds/vcr/qar_cpt_fsl.sh) ----------------------------------------------
@@ -466,17 +539,28 @@ def _qar_layout(questions):
     return n_ans, n_rats
 
 
-def val_vcr_qar(model, questions, device, batch_questions=4, trim=False, bucket=False):
+def val_vcr_qar(model, questions, device, batch_questions=4, trim=False, bucket=False, resident=None):
     """Evaluation pass of vcr_qar_nsp_cpt.py:605-703 (evaluate) on VCRQAR_NSPCPT.  questions: prompts.assemble_vcr_qar dicts with ``img_feats``
     (Li, D).  Questions are sharded over ranks (whole questions per rank); per batch ONE encoder pass runs over both blocks (qar_forward) and the
     choice runs on the device (cpt_vcr_qar_choose); the fixed-shape (n_q, 2) predictions, (n_q, 3) flags and (n_q, n_ans + n_rats) choice scores
     are gathered to every rank.  Accuracies follow the reference: results de-duplicated by questionId (last wins), divided by the number of
     questions; "q_ar" is the reference's "Eval Accuracy".  Returns {"preds", "flags", "scores", "q_ids", "acc": {"q_a", "qa_r", "q_ar"}}.
-    trim / bucket: see the top of this module."""
+    trim / bucket: see the top of this module.
+    resident: a ResidentSet of these questions (resident.upload(resident.from_vcr_qar(questions), device)): both blocks of a batch are gathered on
+    the device by one launch, only ``n_ans``, ``n_rats``, ``label`` and ``q_id`` of the questions are read."""
     model.eval()
     n_ans, n_rats = _qar_layout(questions)
+    plans = {}
 
     def groups_of(lo, hi):
+        if resident is not None:
+            sf = resident.seq_first
+            if resident.tables.get("n_ans") != [n_ans] * len(questions):
+                raise ValueError("val_vcr_qar: the resident set was not built from Q->AR questions of %d answers (resident.from_vcr_qar)" % n_ans)
+            groups, found = _resident_walk(resident, model, len(questions), len(questions) * (n_ans + n_rats), lo, hi, batch_questions, bucket, None,
+                                           trim, device, "val_vcr_qar", order=lambda g: rsd.qar_order(sf, n_ans, [lo + i for i in g]))
+            plans.update(found)
+            return groups
         keys = None
         if bucket:
             keys = [max(_item_length(q[part]["input_mask"], q[part]["input_ids"].shape[1]) for part in ("q_a", "qa_r")) for q in questions[lo:hi]]
@@ -484,7 +568,13 @@ def val_vcr_qar(model, questions, device, batch_questions=4, trim=False, bucket=
 
     def step(idx, lo):
         chunk = [questions[lo + i] for i in idx]
-        qa, qr = _qar_blocks(chunk, device, trim)
+        if resident is not None:                # one launch for both blocks: rows [0, B0) are the Q->A block, the others the QA->R block
+            b = resident.gather(*plans[idx[0]], mask_pos=False)
+            B0 = len(chunk) * n_ans
+            qa, qr = ({"input_ids": b["input_ids"][r], "attention_mask": b["attention_mask"][r], "token_type_ids": b["segment_ids"][r],
+                       "img_feats": b["img_feats"][r]} for r in (slice(0, B0), slice(B0, None)))
+        else:
+            qa, qr = _qar_blocks(chunk, device, trim)
         _, _, sc = model.qar_forward(qa, qr, return_scores=True)
         nq = len(chunk)
         B0 = nq * n_ans
@@ -694,24 +784,42 @@ def _vcr_label(q):
     return int(lb[0] if isinstance(lb, (list, tuple)) else lb)
 
 
-def val_vcr(model, questions, device, batch_questions=8, trim=False, bucket=False):
+def val_vcr(model, questions, device, batch_questions=8, trim=False, bucket=False, resident=None):
     """Evaluation pass of vcr_nsp_cpt.py:583-620 (evaluate) on NSPCPT.  questions: prompts.assemble_vcr dicts with ``img_feats`` (Li, D).
     Questions are sharded over ranks (whole questions per rank); per batch one forward gives the relation scores and ONE launch
     (cpt_nsp_choose) the choice scores 1 - softmax(rel)[:, 1], each question's argmax and its correctness; the fixed-shape predictions, flags
     and (n_q, interval) choice scores are gathered to every rank.  Accuracy as the reference: results de-duplicated by questionId (last wins),
     divided by the number of questions.  Returns {"preds" (n_q,), "correct" (n_q,) uint8, "scores" (n_q, interval), "q_ids", "acc"}.
-    trim / bucket: see the top of this module."""
+    trim / bucket: see the top of this module.
+    resident: a ResidentSet of these questions (resident.upload(resident.from_vcr(questions), device)): the batches are gathered on the device,
+    only ``label`` and ``q_id`` of the questions are read (and the number of choices comes from the set)."""
     model.eval()
-    interval = questions[0]["input_ids"].shape[0]
+    plans = {}
+    if resident is not None:
+        counts = np.diff(resident.seq_first)
+        interval = int(counts[0]) if counts.size else 0
+        if bool((counts != interval).any()):
+            raise ValueError("VCR Q->A: every question of a pass needs the same number of answer choices")
+    else:
+        interval = questions[0]["input_ids"].shape[0]
 
     def groups_of(lo, hi):
+        if resident is not None:
+            groups, found = _resident_walk(resident, model, len(questions), len(questions) * interval, lo, hi, batch_questions, bucket, None, trim,
+                                           device, "val_vcr")
+            plans.update(found)
+            return groups
         return _walk(hi - lo, batch_questions, [_item_length(q["input_mask"], q["input_ids"].shape[1]) for q in questions[lo:hi]] if bucket else None)
 
     def step(idx, lo):
         chunk = [questions[lo + i] for i in idx]
-        b, iv = _vcr_block(chunk, device, trim)
-        if iv != interval:
-            raise ValueError("VCR Q->A: every question of a pass needs the same number of answer choices")
+        if resident is not None:
+            b = resident.gather(*plans[idx[0]], mask_pos=False)
+            b["token_type_ids"] = b["segment_ids"]
+        else:
+            b, iv = _vcr_block(chunk, device, trim)
+            if iv != interval:
+                raise ValueError("VCR Q->A: every question of a pass needs the same number of answer choices")
         rel = model(b["input_ids"], b["token_type_ids"], b["attention_mask"], img_feats=b["img_feats"])[0]
         sc, p, c = scoring.nsp_choose_device(rel, interval, [_vcr_label(q) for q in chunk])
         return p, c, sc.view(len(chunk), interval)

@@ -372,6 +372,33 @@ typedef struct {
  * CPT_ERR_SHAPE / CPT_ERR_NULL / CPT_ERR_ALIGN / CPT_ERR_DTYPE as cpt_trim_batch. */
 int cpt_gather_batch(const cpt_resident_store* store, const int32_t* seq_idx, int B, int Lt_out, int Li_out, int64_t* input_ids_out,
                      int64_t* token_type_out, int64_t* attn_mask_out, int64_t* mask_pos_out, float* img_feats_out, void* stream);
+/* Head tables of a resident set, beside cpt_resident_store (added beside ABI 8; no existing struct, entry point or kernel changed): the rows a
+ * head reads and their labels, for sets whose sequences hold 0, 1 or several [MASK] rows (VG pairs: 1, 2 or 3), one label per sequence (the
+ * relation heads of VCR) or a label grid (the MLM training loops).  All pointers are device pointers; the sequences are the store's, in its order. */
+typedef struct {
+    const int32_t* head_first;  /* [n_seq + 1]: sequence s owns head rows [head_first[s], head_first[s + 1]) ; counts may be 0 */
+    const int32_t* head_pos;    /* [n_heads] position in the PADDED sequence, 0 .. Lt + Li - 1 */
+    const int32_t* head_label;  /* [n_heads] label id, -1 = ignored; NULL when the set has no row labels */
+    const int32_t* seq_label;   /* [n_seq] one label per sequence (NSP heads); NULL when absent */
+    int32_t n_heads;
+} cpt_resident_heads;
+/* cpt_gather_batch with up to four more outputs, still ONE launch; the five outputs of cpt_gather_batch are written as it writes them.
+ * row_first [B + 1] int32 on the device: the exclusive prefix sum of the head counts of the batch's sequences (the host knows it from its tables
+ * and sends it with the index lists); R = row_first[B].  Each of the four outputs may be NULL; EVERY element of every other one is written:
+ *   head_rows_out   [R][2] int64: row row_first[b] + k = (b, position) of the k-th head row of sequence seq_idx[b] -- the (n, 2) (sequence, position)
+ *                   rows cpt_model_fwd_rows takes.  Positions are those of the PADDED sequence, not remapped: the caller chooses Lt_out > p for a
+ *                   text position p and Lt_out == Lt when a region position is read (the rule of cpt_batch_extents).
+ *   head_labels_out [R] int64: the rows' labels.
+ *   label_grid_out  [B][Lt_out + Li_out] int64: -1, and head_label at the row's head positions; cut exactly as attn_mask_out is cut (text column c
+ *                   is padded column c, region column Lt_out + j is padded column Lt + j), by the workgroups that write attn_mask_out.
+ *   seq_label_out   [B] int64.
+ * Indices read from memory are clamped (the sequence, head_first against n_heads, a position against Lt + Li, row_first against R): nothing is read
+ * or written outside the arrays.  Error codes as cpt_gather_batch; CPT_ERR_NULL too for an output whose table is NULL (head_label for
+ * head_labels_out and label_grid_out, seq_label for seq_label_out, row_first for the row outputs). */
+int cpt_gather_batch_heads(const cpt_resident_store* store, const cpt_resident_heads* heads, const int32_t* seq_idx, const int32_t* row_first, int B,
+                           int R, int Lt_out, int Li_out, int64_t* input_ids_out, int64_t* token_type_out, int64_t* attn_mask_out,
+                           int64_t* mask_pos_out, float* img_feats_out, int64_t* head_rows_out, int64_t* head_labels_out, int64_t* label_grid_out,
+                           int64_t* seq_label_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Few-shot training step (Oscar/oscar/fewshot/refcoco_cpt.py:231-249): forward that keeps the
